@@ -27,6 +27,14 @@ Frames are the temporally correlated 'pan' stream (orbx/synth.py) so the
 matcher commits hundreds of matches per pair; c5 uses rectified pairs.
 
 python bench.py [--gpus N --steps K --warmup W --batch B --workload c4]
+A plain run does what the headline figure needs: set-up, W warm-up steps, K
+timed steps of the timed path (the pipelined step; the serial step with
+--serial or without a matcher), the result line.  --dump-outputs DIR then
+writes what the last timed step computed as DIR/<name>.npy (same arguments:
+same frames, same arrays).  --full adds everything else: the serial timed
+loop with per-stage times and roofline entries, the check that the pipelined
+matches equal the serial step's, the host-fed and drop-in latency legs (c4)
+and the CPU baseline.
 --gpus N > 1 without WORLD_SIZE in the environment starts N rank processes
 (one per GPU, before this process touches the GPU); under torchrun
 (WORLD_SIZE set) each process is one rank.
@@ -105,6 +113,15 @@ def parse():
                     help="pipelined step: run the matcher's stream on this many CUs only (HIP CU mask, "
                          "every k-th CU; 0 = all CUs)")
     ap.add_argument("--traffic", default="", help="PMC traffic summary (default profiles/traffic_<workload>.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the serial timed loop with "
+                         "per-stage times and roofline entries, the check that the pipelined matches "
+                         "equal the serial step's, the host-fed and latency legs (c4) and the CPU "
+                         "baseline (--no-latency / --no-cpu-baseline leave those legs out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (keypoints, "
+                         "descriptors, counts, matches; a fixed seeded sample of the frames) to "
+                         "DIR/<name>.npy as float32 (rank 0 only)")
     a = ap.parse_args()
     wl = dict(WORKLOADS[a.workload])
     if a.batch <= 0:
@@ -554,6 +571,43 @@ def host_fed_leg(torch, orbx, plan, mp, wl, args, dev, ref_counts, steps=6, warm
                     "frames)"}
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_BUDGET = 48 << 20  # bytes of float32 in the per-row arrays of one dump
+
+
+def dump_outputs(dirname, torch, orbx, kps, desc, counts, per_row=None, per_frame=None):
+    """The last timed step's results as DIR/<name>.npy, float32: kps [B, kcap,
+    28] u8, desc [B, kcap, 32] u8 and counts [B] i32 of the step's frames,
+    per_row {name: [B, kcap]} and per_frame {name: [B]} tensors that go with
+    them.  A fixed seeded sample of the frames (frames.npy) keeps the dump
+    under DUMP_BUDGET; rows at and past a frame's count are no results (the
+    buffers keep whatever was there) and are written as 0 (per_row: -1)."""
+    per_row, per_frame = per_row or {}, per_frame or {}
+    os.makedirs(dirname, exist_ok=True)
+    B, kcap = int(counts.shape[0]), int(kps.shape[1])
+    cols = len(orbx.KEYPOINT_DTYPE.names) + 32 + len(per_row)
+    nf = max(1, min(B, DUMP_BUDGET // (4 * kcap * cols)))
+    sel = np.sort(np.random.default_rng(0x5EED).choice(B, nf, replace=False))
+    idx = torch.from_numpy(sel).to(counts.device)
+    cnt = counts.index_select(0, idx).cpu().numpy()
+    dead = np.arange(kcap)[None, :] >= cnt[:, None]
+    k = kps.index_select(0, idx).cpu().numpy().view(orbx.KEYPOINT_DTYPE).reshape(nf, kcap)
+    kf = np.stack([k[name].astype(np.float32) for name in k.dtype.names], axis=-1)
+    kf[dead] = 0
+    d = desc.index_select(0, idx).cpu().numpy().astype(np.float32)
+    d[dead] = 0
+    out = {"frames": sel.astype(np.float32), "counts": cnt.astype(np.float32), "keypoints": kf,
+           "descriptors": d}
+    for name, t in per_row.items():
+        a = t.index_select(0, idx).cpu().numpy().astype(np.float32)
+        a[dead] = -1
+        out[name] = a
+    for name, t in per_frame.items():
+        out[name] = t.index_select(0, idx).cpu().numpy().astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 # --------------------------------------------------------------------------- distributed
 _BENCH_OUT = None  # stdout for the bench line once a process group exists (dist_setup)
 
@@ -844,31 +898,42 @@ def main_mono(args, wl):
                 match_buf(pend[0])
                 pend[0] = None
 
-    for _ in range(args.warmup):
-        step()
-    plan.check()
-    torch.cuda.synchronize()
-    test_fault(rank)
-    plan.set_timing(True)
-    if mp:
-        mp.set_timing(True)
-    if multi:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    if multi:
-        dist.barrier()
-    el = time.perf_counter() - t0
-    plan.check()
-    st = plan.stage_times()
-    if mp:
-        for k, v in mp.stage_times().items():
-            if v[1]:
-                st[k] = v
-    el = finish_time(torch, dist, world, dev, el)
+    # the serial timed loop: the headline of --serial (and of c3, which has
+    # no matcher to overlap); beside a pipelined headline it runs with --full
+    # only, with the per-stage timers on (stage times, roofline entries)
+    st, el, last = None, None, (kps, desc, counts)
+    if pipe is None or args.full:
+        for _ in range(args.warmup):
+            step()
+        plan.check()
+        torch.cuda.synchronize()
+        test_fault(rank)
+        if args.full:
+            plan.set_timing(True)
+            if mp:
+                mp.set_timing(True)
+        if multi:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        if multi:
+            dist.barrier()
+        el = time.perf_counter() - t0
+        plan.check()
+        if args.full:
+            st = plan.stage_times()
+            if mp:
+                for k, v in mp.stage_times().items():
+                    if v[1]:
+                        st[k] = v
+        el = finish_time(torch, dist, world, dev, el)
+    else:
+        step()  # untimed: the state the pipelined loop continues from (buffer 0 = a whole batch)
+        plan.check()
+        torch.cuda.synchronize()
     kps_total = int(counts[1:].sum().item())
     nmatch = int(mp.nmatches[:B].sum().item()) if mp else 0
     el_serial = el
@@ -876,10 +941,12 @@ def main_mono(args, wl):
     if pipe is not None:
         plan.set_timing(False)
         mp.set_timing(False)
-        ref12 = mp.match12[:B].clone()
+        ref12 = mp.match12[:B].clone() if args.full else None
         for _ in range(args.warmup):
             pipe()
         torch.cuda.synchronize()
+        if not args.full:
+            test_fault(rank)
         if multi:
             dist.barrier()
         torch.cuda.synchronize()
@@ -896,21 +963,26 @@ def main_mono(args, wl):
         drain_ms = (time.perf_counter() - t1) * 1e3
         for p_ in subplans:
             p_.check()
+        last = bufs[(it[0] - 1) & 1]  # the batch the last timed step extracted
+        kps_total = int(last[2][1:].sum().item())
+        nmatch = int(mp.nmatches[:B].sum().item())
         # the frames are the same every step: the pipelined matches must equal
         # the serial loop's bit for bit
-        same = bool(torch.equal(mp.match12[:B], ref12))
-        if not same:
-            raise SystemExit("bench.py: pipelined matches differ from the serial step")
+        if args.full:
+            same = bool(torch.equal(mp.match12[:B], ref12))
+            if not same:
+                raise SystemExit("bench.py: pipelined matches differ from the serial step")
+    if args.dump_outputs and rank == 0:
+        k_l, d_l, c_l = last
+        dump_outputs(args.dump_outputs, torch, orbx, k_l[1:], d_l[1:], c_l[1:],
+                     per_row={"match12": mp.match12[:B]} if mp else None,
+                     per_frame={"nmatches": mp.nmatches[:B]} if mp else None)
     drec = dist_record(torch, dist, world, local, keypoints_last_batch=kps_total, matches_last_batch=nmatch,
                        pipelined_equals_serial=same)  # collective: every rank
     if rank != 0:
         if multi:
             dist.destroy_process_group()
         return
-    geo = plan.geo
-    by = stage_bytes(geo, B, kps_total, B, wl["topn"], level_blur=st.get("blur", (0, 0))[1] > 0)
-    traffic = load_traffic(args.traffic)
-    per_step, roof, pf = roofline_entries(st, args.steps, by, geo, B, traffic)
     unit = "frames/s"
     metric = "ORB extract%s frames/sec at %dx%d, %d pyramid level%s" % (
         "+match" if match else "", W, H, wl["nlevels"], "s" if wl["nlevels"] > 1 else "")
@@ -931,10 +1003,15 @@ def main_mono(args, wl):
                    "parallelism": "frame-sharded dp%d" % world,
                    "keypoints_last_batch": kps_total, "matches_last_batch": nmatch,
                    "matches_per_pair": round(nmatch / B, 1)},
-        "stages_ms_per_step": {k: round(v, 4) for k, v in per_step.items()},
-        "roofline": roof,
-        "roofline_pyr_fast": pf,
     }
+    if st is not None:  # --full: the serial loop ran with the per-stage timers on
+        geo = plan.geo
+        by = stage_bytes(geo, B, kps_total, B, wl["topn"], level_blur=st.get("blur", (0, 0))[1] > 0)
+        traffic = load_traffic(args.traffic)
+        per_step, roof, pf = roofline_entries(st, args.steps, by, geo, B, traffic)
+        out["stages_ms_per_step"] = {k: round(v, 4) for k, v in per_step.items()}
+        out["roofline"] = roof
+        out["roofline_pyr_fast"] = pf
     if pipe is not None:
         out["step_mode"] = ("pipelined: step k = batch k-1's matching on a second, high-priority stream "
                             "+ batch k's extraction, overlapping (same work per step, matches equal the "
@@ -944,16 +1021,17 @@ def main_mono(args, wl):
                                  % (len(subplans), B // len(subplans), len(subplans),
                                     "the batch matched once all are extracted" if args.match_whole
                                     else "each sub-batch matched as soon as it is extracted"))
-        out["serial"] = {"value": round(world * B * args.steps / el_serial, 2),
-                         "ms_per_step": round(el_serial / args.steps * 1e3, 3),
-                         "note": "stage times and roofline entries come from this serial timed loop "
-                                 "(kernels alone on the GPU)"}
+        if args.full:
+            out["serial"] = {"value": round(world * B * args.steps / el_serial, 2),
+                             "ms_per_step": round(el_serial / args.steps * 1e3, 3),
+                             "note": "stage times and roofline entries come from this serial timed loop "
+                                     "(kernels alone on the GPU)"}
         out["pipeline_drain_ms"] = round(drain_ms, 3)  # untimed: the last batch's matching, after the window
-    if world == 1 and not args.no_latency and args.workload == "c4":
+    if args.full and world == 1 and not args.no_latency and args.workload == "c4":
         out["host_fed"] = host_fed_leg(torch, orbx, plan, mp, wl, args, dev, counts[1:])
         out["latency"] = latency_leg()
     out["distributed"] = drec
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, wl)
     print(json.dumps(out), file=_BENCH_OUT or sys.stdout, flush=True)
     if multi:
@@ -1114,33 +1192,45 @@ def main_c5(args, wl):
                 match_buf(pend[0])
                 pend[0] = None
 
-    for _ in range(args.warmup):
-        step()
-    pl.check()
-    pr.check()
-    sp.check()
-    torch.cuda.synchronize()
-    test_fault(rank)
-    for o in (pl, pr, sp, mp):
-        o.set_timing(True)
-    if multi:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    if multi:
-        dist.barrier()
-    el = time.perf_counter() - t0
-    sp.check()
-    st = {}
-    for o in (pl, pr, sp, mp):
-        for k, v in o.stage_times().items():
-            if v[1]:
-                a = st.get(k, (0.0, 0))
-                st[k] = (a[0] + v[0], a[1] + v[1])
-    el = finish_time(torch, dist, world, dev, el)
+    # the serial timed loop: the headline of --serial; beside the pipelined
+    # headline it runs with --full only, with the per-stage timers on
+    st, el, last, sp_last = None, None, (kps, desc, counts), [sp]
+    if pipe is None or args.full:
+        for _ in range(args.warmup):
+            step()
+        pl.check()
+        pr.check()
+        sp.check()
+        torch.cuda.synchronize()
+        test_fault(rank)
+        if args.full:
+            for o in (pl, pr, sp, mp):
+                o.set_timing(True)
+        if multi:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        if multi:
+            dist.barrier()
+        el = time.perf_counter() - t0
+        sp.check()
+        if args.full:
+            st = {}
+            for o in (pl, pr, sp, mp):
+                for k, v in o.stage_times().items():
+                    if v[1]:
+                        a = st.get(k, (0.0, 0))
+                        st[k] = (a[0] + v[0], a[1] + v[1])
+        el = finish_time(torch, dist, world, dev, el)
+    else:
+        step()  # untimed: the state the pipelined loop continues from (buffer 0 = a whole batch)
+        pl.check()
+        pr.check()
+        sp.check()
+        torch.cuda.synchronize()
     kps_total = int(counts[1:].sum().item()) + int(pr.counts[:B].sum().item())
     nstereo = int(sp.nmatches[:B].sum().item())
     nmatch = int(mp.nmatches[:B].sum().item())
@@ -1149,10 +1239,12 @@ def main_c5(args, wl):
     if pipe is not None:
         for o in (pl, pr, sp, mp):
             o.set_timing(False)
-        ref12 = mp.match12[:B].clone()
+        ref12 = mp.match12[:B].clone() if args.full else None
         for _ in range(args.warmup):
             pipe()
         torch.cuda.synchronize()
+        if not args.full:
+            test_fault(rank)
         if multi:
             dist.barrier()
         torch.cuda.synchronize()
@@ -1169,18 +1261,29 @@ def main_c5(args, wl):
         drain_ms = (time.perf_counter() - t1) * 1e3
         for _, _, sp_j in subs:
             sp_j.check()
-        same = bool(torch.equal(mp.match12[:B], ref12))
-        if not same:
-            raise SystemExit("bench.py: pipelined matches differ from the serial step")
+        last = bufs[(it[0] - 1) & 1]  # the batch the last timed step extracted
+        sp_last = [sp_j for _, _, sp_j in subs]
+        nstereo = sum(int(s_.nmatches[:B // len(subs)].sum().item()) for s_ in sp_last)
+        nmatch = int(mp.nmatches[:B].sum().item())
+        if args.full:
+            same = bool(torch.equal(mp.match12[:B], ref12))
+            if not same:
+                raise SystemExit("bench.py: pipelined matches differ from the serial step")
+    if args.dump_outputs and rank == 0:
+        k_l, d_l, c_l = last
+        n_s = B // len(sp_last)  # every sub-batch's stereo plan holds its own rows
+        dump_outputs(args.dump_outputs, torch, orbx, k_l[1:], d_l[1:], c_l[1:],
+                     per_row={"match12": mp.match12[:B],
+                              "uright": torch.cat([s_.uright[:n_s] for s_ in sp_last]),
+                              "depth": torch.cat([s_.depth[:n_s] for s_ in sp_last])},
+                     per_frame={"nmatches": mp.nmatches[:B],
+                                "stereo_nmatches": torch.cat([s_.nmatches[:n_s] for s_ in sp_last])})
     drec = dist_record(torch, dist, world, local, keypoints_last_batch=kps_total, matches_last_batch=nmatch,
                        stereo_matches_last_batch=nstereo, pipelined_equals_serial=same)  # collective: every rank
     if rank != 0:
         if multi:
             dist.destroy_process_group()
         return
-    by = stage_bytes(pl.geo, 2 * B, kps_total, B, wl["topn"], level_blur=st.get("blur", (0, 0))[1] > 0)
-    traffic = load_traffic(args.traffic)
-    per_step, roof, pf = roofline_entries(st, args.steps, by, pl.geo, 2 * B, traffic)
     out = {
         "metric": "ORB stereo extract+match frames/sec at %dx%d (KITTI-shaped), %d pyramid levels"
                   % (W, H, wl["nlevels"]),
@@ -1204,10 +1307,14 @@ def main_c5(args, wl):
                    "pairs_per_gpu_per_step": B, "parallelism": "frame-sharded dp%d" % world,
                    "keypoints_last_batch": kps_total, "stereo_matches_last_batch": nstereo,
                    "bow_matches_last_batch": nmatch},
-        "stages_ms_per_step": {k: round(v, 4) for k, v in per_step.items()},
-        "roofline": roof,
-        "roofline_pyr_fast": pf,
     }
+    if st is not None:  # --full: the serial loop ran with the per-stage timers on
+        by = stage_bytes(pl.geo, 2 * B, kps_total, B, wl["topn"], level_blur=st.get("blur", (0, 0))[1] > 0)
+        traffic = load_traffic(args.traffic)
+        per_step, roof, pf = roofline_entries(st, args.steps, by, pl.geo, 2 * B, traffic)
+        out["stages_ms_per_step"] = {k: round(v, 4) for k, v in per_step.items()}
+        out["roofline"] = roof
+        out["roofline_pyr_fast"] = pf
     if pipe is not None:
         out["step_mode"] = ("pipelined: step k = batch k-1's SearchByBoW on a second, high-priority "
                             "stream + batch k's extraction and stereo matching, overlapping (same work per "
@@ -1218,13 +1325,14 @@ def main_c5(args, wl):
                                  % (len(subs), sub, len(subs),
                                     "the batch matched once all are extracted" if args.match_whole
                                     else "each sub-batch matched as soon as it is extracted"))
-        out["serial"] = {"value": round(world * B * args.steps / el_serial, 2),
-                         "ms_per_step": round(el_serial / args.steps * 1e3, 3),
-                         "note": "stage times and roofline entries come from this serial timed loop "
-                                 "(kernels alone on the GPU)"}
+        if args.full:
+            out["serial"] = {"value": round(world * B * args.steps / el_serial, 2),
+                             "ms_per_step": round(el_serial / args.steps * 1e3, 3),
+                             "note": "stage times and roofline entries come from this serial timed loop "
+                                     "(kernels alone on the GPU)"}
         out["pipeline_drain_ms"] = round(drain_ms, 3)  # untimed: the last batch's matching, after the window
     out["distributed"] = drec
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c5(args, wl)
     print(json.dumps(out), file=_BENCH_OUT or sys.stdout, flush=True)
     if multi:

@@ -39,11 +39,12 @@ import pytest  # noqa: E402
 @pytest.mark.gpu
 def test_bench_pipelined_step_runs_and_matches_serial():
     # the default bench line times the pipelined step (extraction of step
-    # k+1 overlapping the matching of step k); bench.py itself aborts if its
-    # matches differ from the serial loop's, and reports the serial numbers
+    # k+1 overlapping the matching of step k); with --full bench.py itself
+    # aborts if its matches differ from the serial loop's, and reports the
+    # serial numbers
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--batch", "8",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-latency"],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-latency"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -61,7 +62,8 @@ def test_bench_split_extraction_matches_serial():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     for wl in ("c1", "c5"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", wl, "--batch", "8",
-                            "--split", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-latency"],
+                            "--split", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                            "--no-latency"],
                            env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -78,7 +80,8 @@ def test_bench_two_ranks_pipelined_on_one_gpu():
     env["ORBX_BENCH_SHARE_GPU"] = "1"
     for wl in ("c1", "c5"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", wl,
-                            "--batch", "8", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-latency"],
+                            "--batch", "8", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
+                            "--no-latency"],
                            env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -93,7 +96,7 @@ def test_bench_c4_host_fed_and_latency_legs():
     # and the reference-shaped compat operator()) reports every call site
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c4", "--batch", "8",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                        "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -108,10 +111,13 @@ def test_bench_c4_host_fed_and_latency_legs():
     assert co["operator_with_mvImagePyramid"]["keypoints"] == co["operator_no_pyramid"]["keypoints"]
 
 
-def _bench(args, extra_env=None, timeout=600):
+def _bench(args, extra_env=None, timeout=600, full=True):
+    # full: the serial loop and the pipelined-equals-serial check beside the
+    # headline, without the CPU baseline and the latency legs
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(extra_env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--no-cpu-baseline", "--no-latency"],
+    extra = ["--full", "--no-cpu-baseline", "--no-latency"] if full else []
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra,
                           env=env, capture_output=True, text=True, timeout=timeout)
 
 
@@ -165,3 +171,38 @@ def test_bench_failed_rank_ends_job(fault):
     assert r.returncode != 0
     assert "test fault" in r.stderr
     assert time.time() - t0 < 240
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("wl", ["c1", "c5"])
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(wl, tmp_path):
+    # a plain run times the headline path only (no serial record, stage
+    # times, extra legs); --dump-outputs writes the last timed step's arrays
+    # as float32 .npy: the same arrays from a second run, here a --full one
+    # (whose pipelined loop continues from its serial loop)
+    import numpy as np
+    runs = []
+    for tag, full in (("a", False), ("f", True)):
+        d = tmp_path / tag
+        r = _bench(["--gpus", "1", "--workload", wl, "--batch", "8", "--steps", "3", "--warmup", "1",
+                    "--dump-outputs", str(d)], full=full)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["higher_is_better"] is True and line["dtype"] == "u8" and line["unit"]
+        moved = ("serial", "stages_ms_per_step", "roofline", "host_fed", "latency", "cpu_baseline")
+        if full:
+            assert all(k in line for k in moved[:3])
+        else:
+            assert not any(k in line for k in moved)
+        arrs = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+        assert {"frames", "counts", "keypoints", "descriptors", "match12", "nmatches"} <= set(arrs)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["counts"].min() > 0 and arrs["nmatches"].sum() == line["config"][
+            "matches_last_batch" if wl == "c1" else "bow_matches_last_batch"]
+        runs.append(arrs)
+    for other in runs[1:]:
+        assert set(other) == set(runs[0])
+        for k, a in runs[0].items():
+            assert np.array_equal(a, other[k]), k
