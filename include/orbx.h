@@ -24,7 +24,9 @@ extern "C" {
 
 /* 2 (round 6): plan option flags 2 and 4 retired (ORBX_ERR_ARG), flags 8 / 16,
  * orbx_proj_problem and the orbm_proj_plan_* / orbm_search_by_bow_kf_frame
- * entry points added (round 5) */
+ * entry points added (round 5).  orbx_tri_frame and
+ * orbm_search_for_triangulation are additive (no existing struct or entry
+ * point changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
 /* status codes */
@@ -280,6 +282,51 @@ int orbm_search_by_bow(const orbx_bow_frame* kf1, const orbx_bow_frame* kf2, flo
  * ORBX_ERR_UNSUPPORTED for nnratio <= 50/256 (no second-best could pass). */
 int orbm_search_by_bow_kf_frame(const orbx_bow_frame* kf, const orbx_bow_frame* frame, float nnratio,
                                 int check_ori, int device, int32_t* match_f, int* nmatches);
+
+/* One KeyFrame's inputs to SearchForTriangulation: keys = mvKeysUn (pt, angle
+ * and octave are read), desc = mDescriptors, has_mp[i] != 0 <=>
+ * GetMapPoint(i) != NULL (a pointer test only, no isBad(); NULL = no feature
+ * has one), the FeatureVector flattened as in orbx_bow_frame, and
+ * level_sigma2[nlevels] = mvLevelSigma2. */
+typedef struct {
+  int n;
+  const orbx_keypoint* keys; /* n */
+  const uint8_t* desc;       /* n x 32 */
+  const uint8_t* has_mp;     /* n, or NULL */
+  int nnodes;
+  const uint32_t* node_id;  /* ascending, unique */
+  const uint32_t* node_off; /* nnodes + 1 */
+  const uint32_t* feat;
+  const float* level_sigma2; /* nlevels */
+  int nlevels;
+} orbx_tri_frame;
+
+/* ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:368-467 with
+ * CheckDistEpipolarLine, :71-85) of kf1 against nkf2 neighbour keyframes in
+ * one batch: problem p searches kf1's rows over kf2[p] under F12 + 9 * p (3x3
+ * row-major, CV_32F).  nkf2 = 1 is the reference's call; nkf2 > 1 is the
+ * neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:
+ * 177-191) as one upload, one set of launches and one download.  Per row of a
+ * common vocabulary node (a KF1 feature without a MapPoint): over the node's
+ * KF2 features without a MapPoint, in list order, a candidate with Hamming
+ * distance <= the best so far (50 at first; ties accepted, so the later
+ * candidate wins) that passes the epipolar test becomes the best; with
+ * check_ori (mbCheckOrientation) every such acceptance enters the rotation
+ * histogram, and a row with any acceptance outside the three kept bins is
+ * reset.  match12[p * kf1->n + i] = the index in kf2[p], -1 for none, or -2
+ * where the rotation check reset a match (as orbm_search_by_bow);
+ * nmatches[p] = the entries >= 0 (vMatchedPairs = those rows in ascending i).
+ * only_stereo != 0 (bOnlyStereo) gives no match at all: in this reference the
+ * `!bOnlyStereo &&` of :417 rejects every candidate (mvuRight and the epipole
+ * of :373-379 are therefore not inputs).  Only kf2[p]'s level_sigma2 is read
+ * (kf1's may be NULL).  Host pointers; synchronous.
+ * ORBX_ERR_ARG where the reference would index out of range or count a row
+ * twice: a feat index >= n, a kf2 octave outside [0, nlevels), a kf1 feature
+ * listed twice in feat, node_id not ascending, nkf2 < 0.  nkf2 == 0, n == 0
+ * and no common node are valid (no matches). */
+int orbm_search_for_triangulation(const orbx_tri_frame* kf1, int nkf2, const orbx_tri_frame* kf2,
+                                  const float* F12, int only_stereo, int check_ori, int device,
+                                  int32_t* match12, int* nmatches);
 
 /* ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:896-908), batched on the
  * device: dist[i] = Hamming(a + 32*ia[i], b + 32*ib[i]); host pointers. */

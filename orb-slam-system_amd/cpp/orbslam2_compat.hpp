@@ -14,10 +14,11 @@
 //     include/ORBextractor.h:25-91 (constructor, operator(), the six getters,
 //     public mvImagePyramid);
 //   * ORB_SLAM2::ORBmatcher with ORBmatcher.h's DescriptorDistance and the
-//     two SearchByBoW overloads (include/ORBmatcher.h:20-45) as templates
-//     over the caller's KeyFrame / MapPoint / Frame classes, reading exactly
-//     the members the reference reads (GetMapPointMatches, isBad, mvKeysUn,
-//     mFeatVec, mDescriptors, N).
+//     two SearchByBoW overloads (include/ORBmatcher.h:20-45) and
+//     SearchForTriangulation (:51-52) as templates over the caller's KeyFrame
+//     / MapPoint / Frame classes, reading exactly the members the reference
+//     reads (GetMapPointMatches, GetMapPoint, isBad, mvKeysUn, mFeatVec,
+//     mDescriptors, mvLevelSigma2, N).
 // A project that has OpenCV keeps its cv:: and uses INTEGRATION.md's glue
 // instead; define ORBX_COMPAT_NO_CV to take cv:: from OpenCV headers.
 #ifndef ORBX_ORBSLAM2_COMPAT_HPP
@@ -31,6 +32,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/orbx.h"
@@ -41,6 +43,9 @@
 #endif
 #ifndef CV_8UC1
 #define CV_8UC1 0
+#endif
+#ifndef CV_32F
+#define CV_32F 5
 #endif
 
 namespace cv {
@@ -72,8 +77,10 @@ class Exception : public std::runtime_error {
   Exception(int c, const std::string& msg) : std::runtime_error(msg), code(c) {}
 };
 
-// 2-D CV_8UC1 matrix header over a shared byte buffer (OpenCV value semantics:
-// copies share data, create() reallocates only when the shape changes)
+// 2-D single-channel matrix header (CV_8UC1 images and descriptors; CV_32F for
+// the small float matrices the matcher takes, e.g. F12) over a shared byte
+// buffer (OpenCV value semantics: copies share data, create() reallocates
+// only when the shape changes)
 class Mat {
  public:
   int rows = 0, cols = 0;
@@ -84,14 +91,14 @@ class Mat {
   Mat(int r, int c, int type) { create(r, c, type); }
   // wraps external data (not owned), like cv::Mat(rows, cols, type, data, step)
   Mat(int r, int c, int type, void* d, size_t st = 0)
-      : rows(r), cols(c), data(static_cast<uint8_t*>(d)), step(st ? st : (size_t)c), type_(type) {}
+      : rows(r), cols(c), data(static_cast<uint8_t*>(d)), step(st ? st : (size_t)c * esz(type)), type_(type) {}
 
   void create(int r, int c, int type) {
-    if (buf_ && r == rows && c == cols && type == type_ && step == (size_t)c) return;
-    buf_ = std::make_shared<std::vector<uint8_t>>((size_t)r * c);
+    if (buf_ && r == rows && c == cols && type == type_ && step == (size_t)c * esz(type)) return;
+    buf_ = std::make_shared<std::vector<uint8_t>>((size_t)r * c * esz(type));
     rows = r;
     cols = c;
-    step = (size_t)c;
+    step = (size_t)c * esz(type);
     type_ = type;
     data = buf_->data();
   }
@@ -103,7 +110,8 @@ class Mat {
   }
   bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
   int type() const { return type_; }
-  bool isContinuous() const { return step == (size_t)cols; }
+  bool isContinuous() const { return step == (size_t)cols * esz(type_); }
+  size_t elemSize() const { return esz(type_); }
   template <typename T>
   T* ptr(int r = 0) { return reinterpret_cast<T*>(data + (size_t)r * step); }
   template <typename T>
@@ -123,17 +131,18 @@ class Mat {
   }
   Mat clone() const {
     Mat m(rows, cols, type_);
-    for (int r = 0; r < rows; ++r) memcpy(m.ptr(r), ptr(r), (size_t)cols);
+    for (int r = 0; r < rows; ++r) memcpy(m.ptr(r), ptr(r), (size_t)cols * esz(type_));
     return m;
   }
   void copyTo(Mat& dst) const {
     if (dst.data == data && dst.rows == rows && dst.cols == cols) return;
     Mat src(*this);  // keeps the source alive if dst aliases it
     dst.create(rows, cols, type_);
-    for (int r = 0; r < rows; ++r) memcpy(dst.ptr(r), src.ptr(r), (size_t)cols);
+    for (int r = 0; r < rows; ++r) memcpy(dst.ptr(r), src.ptr(r), (size_t)cols * esz(type_));
   }
 
  private:
+  static size_t esz(int type) { return type == CV_32F ? sizeof(float) : 1; }
   std::shared_ptr<std::vector<uint8_t>> buf_;
   int type_ = CV_8UC1;
 };
@@ -282,8 +291,9 @@ class ORBextractor {
   std::vector<uint8_t> dbuf_;
 };
 
-// ORB_SLAM2::ORBmatcher: DescriptorDistance and SearchByBoW
-// (include/ORBmatcher.h:20-45; src/ORBmatcher.cc:88-119,278-366,896-908).
+// ORB_SLAM2::ORBmatcher: DescriptorDistance, SearchByBoW and
+// SearchForTriangulation (include/ORBmatcher.h:20-52;
+// src/ORBmatcher.cc:88-119,278-366,368-467,896-908).
 class ORBmatcher {
  public:
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;  // ORBmatcher.cc:13-15
@@ -361,6 +371,65 @@ class ORBmatcher {
     return n;
   }
 
+  // SearchForTriangulation(KeyFrame*, KeyFrame*, cv::Mat F12,
+  // vector<pair<size_t, size_t>>&, bOnlyStereo) (:368-467) on the device.  KF:
+  // the reference's KeyFrame (GetMapPoint(i), mvKeysUn, mDescriptors,
+  // mFeatVec, mvLevelSigma2, N); M: a 3x3 matrix with at<float>(r, c)
+  // (cv::Mat, CV_32F).  With bOnlyStereo the reference matches nothing (its
+  // `!bOnlyStereo &&` at :417), and so does this.
+  template <class KF, class M>
+  int SearchForTriangulation(KF* pKF1, KF* pKF2, M F12,
+                             std::vector<std::pair<size_t, size_t> >& vMatchedPairs,
+                             const bool bOnlyStereo) {
+    std::vector<std::vector<std::pair<size_t, size_t> > > vv;
+    const int n = SearchForTriangulation(pKF1, std::vector<KF*>(1, pKF2), std::vector<M>(1, F12), vv,
+                                         bOnlyStereo);
+    vMatchedPairs.swap(vv[0]);
+    return n;
+  }
+
+  // The neighbour loop of LocalMapping::CreateNewMapPoints
+  // (src/LocalMapping.cc:177-191) as one batched device call: pKF1 against
+  // every vpKF2[p] under vF12[p].  vvMatchedPairs[p] is what the single call
+  // returns for neighbour p on the MapPoints as they are now; the return
+  // value is the total number of pairs.  The reference's loop triangulates
+  // between its calls: a caller that adds MapPoints to pKF1 while walking
+  // neighbour p's pairs drops the later pairs whose pKF1 feature has one by
+  // then (exact with checkOri = false, as CreateNewMapPoints builds its
+  // matcher).
+  template <class KF, class M>
+  int SearchForTriangulation(KF* pKF1, const std::vector<KF*>& vpKF2, const std::vector<M>& vF12,
+                             std::vector<std::vector<std::pair<size_t, size_t> > >& vvMatchedPairs,
+                             const bool bOnlyStereo) {
+    if (vpKF2.size() != vF12.size()) orbx_throw(ORBX_ERR_ARG, "SearchForTriangulation");
+    const size_t nk = vpKF2.size(), n1 = pKF1->N > 0 ? (size_t)pKF1->N : 0;
+    TriFlat f1;
+    flatten_tri(pKF1, f1);
+    std::vector<TriFlat> f2(nk);
+    std::vector<orbx_tri_frame> frames(nk);
+    std::vector<float> F(nk * 9);
+    for (size_t p = 0; p < nk; ++p) {
+      flatten_tri(vpKF2[p], f2[p]);
+      frames[p] = f2[p].f;
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) F[p * 9 + 3 * r + c] = vF12[p].template at<float>(r, c);
+    }
+    std::vector<int32_t> m12(nk * n1 ? nk * n1 : 1, -1);
+    std::vector<int> nm(nk ? nk : 1, 0);
+    orbx_throw(orbm_search_for_triangulation(&f1.f, (int)nk, frames.data(), F.data(), bOnlyStereo ? 1 : 0,
+                                             mbCheckOrientation ? 1 : 0, 0, m12.data(), nm.data()),
+               "SearchForTriangulation");
+    vvMatchedPairs.assign(nk, std::vector<std::pair<size_t, size_t> >());
+    int total = 0;
+    for (size_t p = 0; p < nk; ++p) {
+      vvMatchedPairs[p].reserve(nm[p]);  // :459-465
+      for (size_t i = 0; i < n1; ++i)
+        if (m12[p * n1 + i] >= 0) vvMatchedPairs[p].push_back(std::make_pair(i, (size_t)m12[p * n1 + i]));
+      total += nm[p];
+    }
+    return total;
+  }
+
  protected:
   struct Flat {
     orbx_bow_frame f;
@@ -408,6 +477,33 @@ class ORBmatcher {
     o.f.node_id = o.ids.data();
     o.f.node_off = o.off.data();
     o.f.feat = o.feat.data();
+  }
+
+  struct TriFlat {
+    orbx_tri_frame f;
+    std::vector<uint8_t> mp;
+    std::vector<uint32_t> ids, off, feat;
+  };
+  template <class KF>
+  static void flatten_tri(KF* kf, TriFlat& o) {
+    o.mp.resize(kf->N > 0 ? (size_t)kf->N : 0);
+    for (int i = 0; i < kf->N; ++i) o.mp[i] = kf->GetMapPoint(i) != nullptr;  // no isBad() (:399,409)
+    o.off.push_back(0);
+    for (const auto& node : kf->mFeatVec) {  // std::map: ascending NodeId
+      o.ids.push_back(node.first);
+      o.feat.insert(o.feat.end(), node.second.begin(), node.second.end());
+      o.off.push_back((uint32_t)o.feat.size());
+    }
+    o.f.n = kf->N;
+    o.f.keys = reinterpret_cast<const orbx_keypoint*>(kf->mvKeysUn.data());
+    o.f.desc = kf->mDescriptors.data;
+    o.f.has_mp = o.mp.data();
+    o.f.nnodes = (int)o.ids.size();
+    o.f.node_id = o.ids.data();
+    o.f.node_off = o.off.data();
+    o.f.feat = o.feat.data();
+    o.f.level_sigma2 = kf->mvLevelSigma2.data();
+    o.f.nlevels = (int)kf->mvLevelSigma2.size();
   }
 
   float mfNNratio;

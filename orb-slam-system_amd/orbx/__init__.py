@@ -5,6 +5,7 @@ reference interfaces for tests and the benchmark:
 
   Extractor      ORB_SLAM2::ORBextractor  (/root/reference/include/ORBextractor.h:25-91)
   search_by_bow  ORBmatcher::SearchByBoW(KF, KF) (/root/reference/src/ORBmatcher.cc:278-366)
+  search_for_triangulation  ORBmatcher::SearchForTriangulation, batched (ORBmatcher.cc:368-467)
   compute_stereo_matches  Frame::ComputeStereoMatches (/root/reference/src/Frame.cc:446-620)
   descriptor_distance_batch  ORBmatcher::DescriptorDistance (ORBmatcher.cc:896-908)
   Plan / MatchPlan  batched device-resident throughput path (bench.py)
@@ -61,7 +62,7 @@ EXPORTED = [
     "orbv_transform", "orbv_transform_batch", "orbv_check", "orbm_search_by_projection",
     "orbm_proj_plan_create", "orbm_proj_plan_destroy", "orbm_proj_plan_search",
     "orbm_compute_distinctive_descriptors", "orbx_undistort_keypoints", "orbx_selftest_sincos",
-    "orbx_selftest_sincos_range",
+    "orbx_selftest_sincos_range", "orbm_search_for_triangulation",
 ]
 
 
@@ -114,6 +115,17 @@ class BowFrame(ctypes.Structure):
                 ("node_off", ctypes.c_void_p), ("feat", ctypes.c_void_p)]
 
 
+class TriFrame(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("keys", ctypes.c_void_p), ("desc", ctypes.c_void_p),
+                ("has_mp", ctypes.c_void_p), ("nnodes", ctypes.c_int), ("node_id", ctypes.c_void_p),
+                ("node_off", ctypes.c_void_p), ("feat", ctypes.c_void_p),
+                ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)]
+
+
+# k_tri_search's tile (csrc/tri_internal.h): KF1 rows per wavefront and KF2
+# list entries staged in LDS at a time
+TRI_ROWS, TRI_CHUNK = 64, 64
+
 P, I, F, SZ = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 _sig = {
     "orbx_abi_version": (I, []),
@@ -149,6 +161,7 @@ _sig = {
     "orbx_synth_frames": (I, [P, I, I, SZ, I, I, I, P]),
     "orbm_search_by_bow": (I, [P, P, F, I, I, P, P]),
     "orbm_search_by_bow_kf_frame": (I, [P, P, F, I, I, P, P]),
+    "orbm_search_for_triangulation": (I, [P, I, P, P, I, I, I, P, P]),
     "orbm_descriptor_distance_batch": (I, [P, I, P, I, P, P, I, I, P]),
     "orbm_plan_create": (I, [I, I, I, I, P]),
     "orbm_plan_destroy": (I, [P]),
@@ -459,6 +472,45 @@ def search_by_bow_kf_frame(kf, fr, nnratio=0.6, check_ori=True, device=0):
                                             1 if check_ori else 0, device, _p(m), ctypes.byref(nm)),
            "orbm_search_by_bow_kf_frame")
     return m[:b2.n].copy(), nm.value
+
+
+def tri_struct(k, keep):
+    """orbx_tri_frame of dict(keys, desc, has_mp|None, node_id, off, feat,
+    level_sigma2|None); the arrays it points into are appended to keep."""
+    keys = np.ascontiguousarray(k["keys"], KEYPOINT_DTYPE)
+    desc = np.ascontiguousarray(k["desc"], np.uint8).reshape(-1, 32)
+    mp = None if k.get("has_mp") is None else np.ascontiguousarray(k["has_mp"], np.uint8)
+    nid = np.ascontiguousarray(k["node_id"], np.uint32)
+    off = np.ascontiguousarray(k["off"], np.uint32)
+    feat = np.ascontiguousarray(k["feat"], np.uint32)
+    s2 = None if k.get("level_sigma2") is None else np.ascontiguousarray(k["level_sigma2"], np.float32)
+    keep.extend([keys, desc, mp, nid, off, feat, s2])
+    return TriFrame(len(keys), _p(keys), _p(desc), _p(mp), len(nid), _p(nid), _p(off), _p(feat),
+                    _p(s2), 0 if s2 is None else len(s2))
+
+
+def search_for_triangulation(kf1, kf2_list, F12_list, only_stereo=False, check_ori=True, device=0):
+    """ORBmatcher::SearchForTriangulation(KF1, KF2, F12, ..) for every KF2 of
+    kf2_list in one batched call (the neighbour loop of CreateNewMapPoints).
+    Frames are dicts (tri_struct); F12_list holds one 3x3 float32 matrix per
+    KF2.  Returns (match12 int32[len(kf2_list), N1], nmatches int32[len(kf2_list)]);
+    vMatchedPairs of problem p = [(i, match12[p, i]) for i where match12[p, i] >= 0]."""
+    keep = []
+    b1 = tri_struct(kf1, keep)
+    nk = len(kf2_list)
+    arr = (TriFrame * max(nk, 1))()
+    for p, k in enumerate(kf2_list):
+        arr[p] = tri_struct(k, keep)
+    F12 = np.ascontiguousarray(np.asarray(F12_list, np.float32).reshape(-1, 9))
+    if len(F12) != nk:
+        raise OrbxError(ERR_ARG, "one F12 per KF2 expected")
+    m = np.full(max(nk * b1.n, 1), -1, np.int32)
+    nm = np.zeros(max(nk, 1), np.int32)
+    _check(_lib.orbm_search_for_triangulation(ctypes.byref(b1), nk, ctypes.cast(arr, ctypes.c_void_p),
+                                              _p(F12), 1 if only_stereo else 0,
+                                              1 if check_ori else 0, device, _p(m), _p(nm)),
+           "orbm_search_for_triangulation")
+    return m[:nk * b1.n].reshape(nk, b1.n).copy(), nm[:nk].copy()
 
 
 def descriptor_distance_batch(a, b, ia, ib, device=0):
