@@ -184,6 +184,13 @@ int orbx_plan_check(orbx_plan* plan, void* stream);
  * stream): FAST strips whose corner list overflowed into the strength-map
  * scan (see orbx_debug_set_fast_ccap). */
 int orbx_plan_debug_counters(orbx_plan* plan, int* fast_overflow_strips);
+/* A second debug counter, read and reset the same way: FAST strips that took
+ * the dense post-pass (row masks, all four waves) since the last call.  With
+ * automatic options those are the strips with more than 64 corners (or more
+ * than the corner list holds); strips with 1..64 corners are finished by one
+ * wave in registers and empty strips only clear their cells' counts, and
+ * neither is counted.  With ORBX_PLAN_FAST_DENSE it counts every strip. */
+int orbx_plan_fast_dense_strips(orbx_plan* plan, int* fast_dense_strips);
 /* Testing only: plans created after this call give the FAST kernels a
  * corner list of `ccap` entries (<= 1024) in one launch group, so the
  * strength-map overflow path runs on ordinary frames; ccap < 0 restores the
@@ -197,7 +204,10 @@ int orbx_debug_set_fast_ccap(int ccap);
  *   ORBX_PLAN_BRIEF_PATCH  descriptors blur each keypoint's 43 x 48 patch
  *                          (k_orient_brief);
  *   ORBX_PLAN_BRIEF_LEVEL  every unique level is blurred once (k_blur) and
- *                          the descriptors sample it (k_orient_brief_lb).
+ *                          the descriptors sample it (k_orient_brief_lb);
+ *   ORBX_PLAN_FAST_DENSE   every FAST strip takes the dense post-pass, as
+ *                          before the per-strip choice (DESIGN.md §4 round 7;
+ *                          for A/B timing and tests).
  * Automatic (0): the tile pyramid, and the level blur when nfeatures x 43 x
  * 48 exceeds ORBX_LB_RATIO x the unique level pixels.
  * The round-4 row-streaming pyramid and fused pyramid + FAST kernels (flags
@@ -207,6 +217,7 @@ int orbx_debug_set_fast_ccap(int ccap);
 #define ORBX_PLAN_PYR_TILES 1
 #define ORBX_PLAN_BRIEF_PATCH 8
 #define ORBX_PLAN_BRIEF_LEVEL 16
+#define ORBX_PLAN_FAST_DENSE 64
 int orbx_plan_set_options(orbx_plan* plan, int flags);
 
 /* mvImagePyramid[level] of frame `frame` of the last orbx_plan_extract on

@@ -142,7 +142,7 @@ static void plan_free(orbx_plan* p) {
   hipSetDevice(p->device);
   void* bufs[] = {p->d_lv, p->d_cells, p->d_strips, p->d_xofs, p->d_xofs1, p->d_yofs, p->d_alpha, p->d_beta,
                   p->d_pyr, p->d_blur, p->d_slots, p->d_ccount, p->d_qkeys, p->d_qout, p->d_qperm,
-                  p->d_qnode, p->d_lcount, p->d_err, p->d_pyr_xs, p->d_pyr_ys, p->d_pyr_bo, p->d_pyr_blob};
+                  p->d_qnode, p->d_lcount, p->d_err, p->d_fs_cnt, p->d_pyr_xs, p->d_pyr_ys, p->d_pyr_bo, p->d_pyr_blob};
   for (void* b : bufs)
     if (b) hipFree(b);
   p->timer.release();
@@ -255,6 +255,11 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
     const int cg0 = (si.lead16 + 3) >> 2, cg1 = (si.lead16 + si.w) >> 2;
     const int cgb = cg0 - (((si.lead16 + 3) & 3) != 3 ? 1 : 0);
     si.cw16 = si.colwalk && si.h - 6 <= (FS_NT / 64) * FS_CW_RMAX && cg1 - cgb <= 63;
+    // the column walk's last wave loads up to FS_CW_RMAX rows below the tile
+    // (never used; the buffer range check does not cover the row offset):
+    // they must be rows of the level.  Cells end at least 16 rows above the
+    // level's last row, so this holds for every plan the geometry accepts
+    if (si.colwalk && si.y + si.h + FS_CW_RMAX > P.levels[si.level].h) { plan_free(p); return ORBX_ERR_UNSUPPORTED; }
     si.soff16 = si.level == 0 ? 0 : si.off + (long long)si.y * si.pitch + (si.x - si.lead16);
   }
   // plans with a pyramid run its waves and FAST's at a raised issue
@@ -407,13 +412,15 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
       dev_alloc((void**)&p->d_qout, B * p->qout_stride * 4) ||
       dev_alloc((void**)&p->d_qperm, B * p->qout_stride * 4) ||
       dev_alloc((void**)&p->d_lcount, B * (size_t)P.params.nlevels * 4) ||
-      dev_alloc((void**)&p->d_err, 16)) {
+      dev_alloc((void**)&p->d_err, 16) ||
+      dev_alloc((void**)&p->d_fs_cnt, sizeof(int) * FS_CNT_LINES * FS_CNT_STRIDE)) {
     plan_free(p);
     return ORBX_ERR_HIP;
   }
   // stream-ordered: no device-wide synchronisation (other extractors and
   // the matcher may be running on this device from other threads)
   if (hipMemsetAsync(p->d_err, 0, 16, us) != hipSuccess ||
+      hipMemsetAsync(p->d_fs_cnt, 0, sizeof(int) * FS_CNT_LINES * FS_CNT_STRIDE, us) != hipSuccess ||
       hipMemsetAsync(p->d_ccount, 0, B * (size_t)(P.ncells ? P.ncells : 1) * 4, us) != hipSuccess ||
       hipStreamSynchronize(us) != hipSuccess) { plan_free(p); return ORBX_ERR_HIP; }
   *out = p;
@@ -461,6 +468,7 @@ static int extract_pass(orbx_plan* p, const uint8_t* frames, int n, size_t fstri
   // decisions when the frames are 16-B aligned)
   LevelArgs la = p->largs;
   la.l0al16 = ((reinterpret_cast<uintptr_t>(frames) | (uintptr_t)fstride | (uintptr_t)rstride) & 15) == 0;
+  la.fast_dense = (p->options & ORBX_PLAN_FAST_DENSE) ? 1 : 0;
   auto fast_launch = [&](int g, int strip0, int strip1, hipStream_t st) {
     if (strip1 <= strip0) return;
     const orbx_plan::FsGroup& G = p->fs_grp[g];
@@ -468,7 +476,7 @@ static int extract_pass(orbx_plan* p, const uint8_t* frames, int n, size_t fstri
                        frames, fstride, rstride, d_pyr, p->pyr_stride, la, p->d_cells,
                        p->d_strips, d_slots, p->slot_stride, d_ccount, P.ncells, P.ini_th,
                        P.min_th, p->fs_tpitch, G.tmaxh, G.mcells, G.ccap,
-                       p->d_err + ORBX_ERRW_FAST_OVF, strip0, p->dbg);
+                       p->d_fs_cnt, strip0, p->dbg);
   };
   const bool overlap = p->overlap && p->s_aux && P.nstrips_l0 > 0;
   if (overlap) {
@@ -612,7 +620,7 @@ extern "C" int orbx_plan_check(orbx_plan* p, void* stream) {
 }
 
 extern "C" int orbx_plan_set_options(orbx_plan* p, int flags) {
-  if (!p || (flags & ~(ORBX_PLAN_PYR_TILES | ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL)) ||
+  if (!p || (flags & ~(ORBX_PLAN_PYR_TILES | ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL | ORBX_PLAN_FAST_DENSE)) ||
       (flags & (ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL)) == (ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL))
     return ORBX_ERR_ARG;
   if ((flags & ORBX_PLAN_BRIEF_LEVEL) && !p->d_blur) {
@@ -643,17 +651,35 @@ extern "C" int orbx_plan_level(orbx_plan* p, int frame, int level, uint8_t* dst,
   return ORBX_OK;
 }
 
+// k_fast_strips' striped debug counters: fetched and cleared on the device,
+// summed into the plan's two totals; each entry returns and resets its own
+static int fs_counters_fetch(orbx_plan* p) {
+  ORBX_TRY(hipSetDevice(p->device));
+  int h[FS_CNT_LINES * FS_CNT_STRIDE];
+  ORBX_TRY(hipMemcpyAsync(h, p->d_fs_cnt, sizeof(h), hipMemcpyDeviceToHost, p->stream));
+  ORBX_TRY(hipStreamSynchronize(p->stream));
+  ORBX_TRY(hipMemsetAsync(p->d_fs_cnt, 0, sizeof(h), p->stream));
+  ORBX_TRY(hipStreamSynchronize(p->stream));
+  for (int l = 0; l < FS_CNT_LINES; ++l) {
+    p->fs_dense_total += h[l * FS_CNT_STRIDE];
+    p->fs_ovf_total += h[l * FS_CNT_STRIDE + 1];
+  }
+  return ORBX_OK;
+}
+
 extern "C" int orbx_plan_debug_counters(orbx_plan* p, int* fast_overflow_strips) {
   if (!p || !fast_overflow_strips) return ORBX_ERR_ARG;
-  ORBX_TRY(hipSetDevice(p->device));
-  int v = 0;
-  ORBX_TRY(hipMemcpyAsync(&p->h_err[ORBX_ERRW_FAST_OVF], p->d_err + ORBX_ERRW_FAST_OVF, sizeof(int),
-                          hipMemcpyDeviceToHost, p->stream));
-  ORBX_TRY(hipStreamSynchronize(p->stream));
-  v = p->h_err[ORBX_ERRW_FAST_OVF];
-  ORBX_TRY(hipMemsetAsync(p->d_err + ORBX_ERRW_FAST_OVF, 0, sizeof(int), p->stream));
-  ORBX_TRY(hipStreamSynchronize(p->stream));
-  *fast_overflow_strips = v;
+  if (const int rc = fs_counters_fetch(p)) return rc;
+  *fast_overflow_strips = (int)p->fs_ovf_total;
+  p->fs_ovf_total = 0;
+  return ORBX_OK;
+}
+
+extern "C" int orbx_plan_fast_dense_strips(orbx_plan* p, int* fast_dense_strips) {
+  if (!p || !fast_dense_strips) return ORBX_ERR_ARG;
+  if (const int rc = fs_counters_fetch(p)) return rc;
+  *fast_dense_strips = (int)p->fs_dense_total;
+  p->fs_dense_total = 0;
   return ORBX_OK;
 }
 

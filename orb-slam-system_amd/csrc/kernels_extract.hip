@@ -512,6 +512,7 @@ __device__ __forceinline__ int wave_excl_scan(int n, int lane, int* total) {
 // ---------------------------------------------------------------------------
 // TP: the tile pitch as a compile-time constant (every LDS offset of stage A
 // an immediate of one address register), 0 = runtime pitch
+static_assert(ORBX_STRIP_MAXCELLS <= 64, "the sparse post-pass keeps a strip's cell counts in one wave's lanes");
 template <int TP>
 __device__ __forceinline__ void fs_strip_body(
     uint8_t* __restrict__ tile, uint8_t* __restrict__ amap_mem, int* __restrict__ cnt,
@@ -520,7 +521,8 @@ __device__ __forceinline__ void fs_strip_body(
     int* __restrict__ cslot, int& ncorner, const StripInfo& st, int f, int lead, int xal,
     int slot_pref, uint32_t* __restrict__ slots, size_t slot_stride,
     uint32_t* __restrict__ ccount, int ncells, int ini_th, int min_th, int tpitch_rt, int ccap,
-    int* __restrict__ ovf, int dbg, const uint8_t* __restrict__ gsrc, int gpitch, bool cw, int kxs) {
+    int* __restrict__ ovf, int dbg, const uint8_t* __restrict__ gsrc, int gpitch, bool cw, int kxs,
+    bool force_dense) {
   const int tpitch = TP ? TP : tpitch_rt;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform: list bases in SGPRs
@@ -787,10 +789,13 @@ __device__ __forceinline__ void fs_strip_body(
       const uint32_t tl = lact ? tt : 0xFF00FF00u;
       if (rb < re) {  // wave-uniform
         uint32_t V[FS_CW_RMAX + 6];
-        // the wave's rows through a buffer resource over [row rb, the tile's
-        // last row]: one scalar offset add per row, no 64-bit address math,
-        // and rows past the tile read 0 from the range check instead of a
-        // clamped address (those rows are never stored or tested; round 6)
+        // the wave's rows through a buffer resource based at row rb: one
+        // scalar offset add per row, no 64-bit address math and no clamped
+        // address.  The row term travels in soffset, which the range check
+        // does not cover (it tests the lane's column offset only), so the
+        // rows a short last wave loads past the tile (at most FS_CW_RMAX of
+        // them; never stored or tested) are read from memory: the planner
+        // checks that they lie inside the level (orbx_plan_create; round 6)
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<uint8_t*>(gsrc) + __umul24((uint32_t)rb, (uint32_t)gpitch), 0, (st.h - rb) * gpitch, 0x00020000);
         const int voff = 4 * gl;
@@ -896,21 +901,21 @@ __device__ __forceinline__ void fs_strip_body(
     if (n2 > 0) strength_batch(lane < n2 ? (int)L2[lane] : 0, lane < n2);
   }
 #ifdef FS_PROBE_NOAPP
-  if (probe_sink == 0x9E3779B9u) ovf[1] = 1;
+  if (probe_sink == 0x9E3779B9u) ovf[2] = 1;
 #endif
   __syncthreads();
   if (dbg == 2) return;
-  for (int i = tid; i < st.ncells * bh; i += FS_NT) mask[i] = mask2[i] = 0ull;  // over the dead tile
-  __syncthreads();
   // pass 2: cv::FAST NMS over the (sparse) nonzero strength map at both
-  // thresholds in one scan: iniThFAST into mask (+ per-cell counts) and
-  // minThFAST into mask2, used for cells left empty at iniThFAST (:293-296)
+  // thresholds in one scan: kept at iniThFAST, and kept at minThFAST, used
+  // for cells left empty at iniThFAST (:293-296)
   const int wcell = st.wcell;
   // (c - c0) / wcell through the float reciprocal (exact: c - c0 < 512)
   const float rwcell = __builtin_amdgcn_rcpf((float)wcell);
-  auto nms_pixel = [&](int r, int c, int a) {
-    const int k = min((int)(((float)(c - c0) + 0.5f) * rwcell), st.ncells - 1);
-    const int cb0 = c0 + k * wcell, cb1 = (k == st.ncells - 1) ? c1 : cb0 + wcell;
+  // the corner's cell k, the cell's first band column and the two kept flags
+  auto nms_kept = [&](int r, int c, int a, int& k, int& cb0, bool& keep_ini, bool& keep_min) {
+    k = min((int)(((float)(c - c0) + 0.5f) * rwcell), st.ncells - 1);
+    cb0 = c0 + k * wcell;
+    const int cb1 = (k == st.ncells - 1) ? c1 : cb0 + wcell;
     // the neighbours' largest strength first: the per-threshold score
     // a > th ? a - 1 : 0 is non-decreasing in a, so its maximum over the
     // neighbours is the score of their maximum (one max per neighbour
@@ -928,14 +933,93 @@ __device__ __forceinline__ void fs_strip_body(
     int mx = max(max(vu ? nu : 0, vd ? nd : 0), max(vl ? nl : 0, vr ? nr : 0));
     mx = max(mx, max(max(vu && vl ? nul : 0, vu && vr ? nur : 0), max(vd && vl ? ndl : 0, vd && vr ? ndr : 0)));
     const int nbm = max(0, mx > min_th ? mx - 1 : 0), nbi = max(0, mx > ini_th ? mx - 1 : 0);
+    keep_ini = a > ini_th && a - 1 > nbi;
+    keep_min = a > min_th && a - 1 > nbm;
+  };
+  const int nc = __builtin_amdgcn_readfirstlane(ncorner);  // workgroup-uniform after the barrier
+  uint32_t* fslots = slots + (size_t)f * slot_stride;
+  if (!force_dense) {
+    // the post-pass by what the strip holds (round 7; on the bench stream 39 %
+    // of the strips hold no corner and 58 % hold 1..64): the row masks, their
+    // zeroing, two more workgroup barriers and the four waves' per-cell scans
+    // below only pay for strips with many corners
+    if (nc == 0) {
+      // empty strip: every cell's count is still written on every call
+      // (d_ccount is zeroed at plan creation only and the quadtree reads it)
+      if (tid < st.ncells) ccount[(size_t)f * ncells + st.cell_begin + tid] = 0u;
+      return;
+    }
+    if (nc <= 64 && nc <= ccap) {
+      // sparse strip: wave 0 alone, one corner per lane, in registers; no
+      // further barrier, mask / mask2 / cnt untouched (static_assert below:
+      // a strip's cells fit the wave's lanes)
+      if (wave != 0) return;
+      int e = 0, c = 0, r = 0, a = 0, k = -1, cb0 = 0;
+      bool ki = false, km = false;
+      if (lane < nc) {
+        e = clist[lane];
+        r = e >> 9;
+        c = e & 511;
+        a = amap[__mul24(r, tpitch) + c];
+        nms_kept(r, c, a, k, cb0, ki, km);
+      }
+      if (dbg == 3 || dbg == 4) return;
+      // per cell that holds a kept corner: the lanes kept at iniThFAST if
+      // there are any, else those kept at minThFAST (cnt[k] != 0 ? mask :
+      // mask2); their number is the cell's count (kept in lane k) and a
+      // lane's slot the number of them earlier in raster order, which is the
+      // order of the list entries r << 9 | c
+      const unsigned long long bal_i = __ballot(ki), bal_m = __ballot(km);
+      unsigned long long rem = bal_i | bal_m;
+      int ncell = 0, rank = 0;
+      bool sel = false;
+      while (rem) {  // wave-uniform
+        const int kc = __builtin_amdgcn_readlane(k, __ffsll(rem) - 1);
+        const unsigned long long same = __ballot(k == kc);
+        rem &= ~same;
+        const bool use_ini = (same & bal_i) != 0ull;
+        const unsigned long long s = same & (use_ini ? bal_i : bal_m);
+        if (lane == kc) ncell = __popcll(s);
+        int before = 0;
+        for (unsigned long long t = s; t; t &= t - 1)
+          before += __builtin_amdgcn_readlane(e, __ffsll(t) - 1) < e ? 1 : 0;
+        if (k == kc && (use_ini ? ki : km)) {
+          rank = before;
+          sel = true;
+        }
+      }
+      if (sel)
+        fslots[cslot[k] + rank] = orbx_pack_key((uint32_t)(xal + c - ORBX_MINB), (uint32_t)(st.y + r - ORBX_MINB),
+                                                (uint32_t)a - 1u, kxs);
+      if (lane < st.ncells) ccount[(size_t)f * ncells + st.cell_begin + lane] = (uint32_t)ncell;
+      return;
+    }
+  }
+  // dense strip (or the plan forces this path, ORBX_PLAN_FAST_DENSE): iniThFAST
+  // into mask (+ per-cell counts) and minThFAST into mask2
+  // debug counters, one lane per dense strip: the strips that came here, and
+  // below those whose corner list overflowed.  The counters are striped over
+  // FS_CNT_LINES 128-B lines (the host sums them): on one address, a frame of
+  // dense strips (noise, or ORBX_PLAN_FAST_DENSE) queued 837 atomics per
+  // 1080p frame behind each other, measured +4.6 % extraction time per
+  // counter
+  int* const fcnt = ovf + ((blockIdx.x + blockIdx.y) & (FS_CNT_LINES - 1)) * FS_CNT_STRIDE;
+#ifndef FS_PROBE_NOCOUNT  // profiling only: the dense path without its counter
+  if (tid == 0) atomicAdd(fcnt, 1);  // orbx_plan_fast_dense_strips
+#endif
+  for (int i = tid; i < st.ncells * bh; i += FS_NT) mask[i] = mask2[i] = 0ull;  // over the dead tile
+  __syncthreads();
+  auto nms_pixel = [&](int r, int c, int a) {
+    int k, cb0;
+    bool ki, km;
+    nms_kept(r, c, a, k, cb0, ki, km);
     const unsigned long long bit = 1ull << (c - cb0);
-    if (a > ini_th && a - 1 > nbi) {
+    if (ki) {
       atomicOr(&mask[k * bh + (r - 3)], bit);
       atomicAdd(&cnt[k], 1);
     }
-    if (a > min_th && a - 1 > nbm) atomicOr(&mask2[k * bh + (r - 3)], bit);
+    if (km) atomicOr(&mask2[k * bh + (r - 3)], bit);
   };
-  const int nc = ncorner;
   if (nc <= ccap) {
     for (int q = tid; q < nc; q += FS_NT) {
       const int e = clist[q];
@@ -943,7 +1027,7 @@ __device__ __forceinline__ void fs_strip_body(
       nms_pixel(r, c, amap[r * tpitch + c]);
     }
   } else {  // list overflow: scan the strength map
-    if (tid == 0) atomicAdd(ovf, 1);  // strips that took this path (orbx_plan_debug_counters)
+    if (tid == 0) atomicAdd(fcnt + 1, 1);  // strips that took this path (orbx_plan_debug_counters)
     const int dr = FS_NT / ng, dg = FS_NT - dr * ng;
     int r = 3 + tid / ng, g = g0 + tid % ng;
     for (; r < 3 + bh;) {
@@ -965,7 +1049,6 @@ __device__ __forceinline__ void fs_strip_body(
   if (dbg == 3 || dbg == 4) return;
   // pass 4: raster-order output per cell: one wave per cell, lane = band row,
   // row offsets by a wave prefix sum of the row popcounts
-  uint32_t* fslots = slots + (size_t)f * slot_stride;
 #ifndef FS_OUT_ONE_CELL
   if (bh <= 32) {
     // two cells per wave (lane halves), so a wave walks its cells' corners
@@ -1124,7 +1207,7 @@ __device__ __forceinline__ void fs_kernel(
   }
   fs_strip_body<TP>(tile, amap_mem, cnt, mask, mask2, wlist1, wlist2, clist, cslot, ncorner, st, f, lead,
                              xal, slot_pref, slots, slot_stride, ccount, ncells, ini_th, min_th, tpitch, ccap, ovf,
-                             dbg, s0, pitch, cw, LA.key_xs);
+                             dbg, s0, pitch, cw, LA.key_xs, LA.fast_dense != 0);
 }
 
 #define FS_KERNEL_ARGS                                                                              \

@@ -104,6 +104,7 @@ struct LevelArgs {
   int key_xs; /* orbx_pack_key shift */
   int prio;   /* 1: FAST waves at ORBX_EX_PRIO */
   int l0al16; /* per launch: the call's frames, frame and row strides are 16-B aligned */
+  int fast_dense; /* per launch: ORBX_PLAN_FAST_DENSE, every strip takes the dense post-pass */
 };
 #define ORBX_STRIP_MAXCELLS 64 /* cells per FAST strip (>= 256 / min cell width) */
 
@@ -130,8 +131,12 @@ struct StereoArgs {
 #define FS_CCAP_MIN 384
 #endif
 #endif
-/* d_err[ORBX_ERRW_FAST_OVF]: strips whose corner list overflowed (debug counter) */
-#define ORBX_ERRW_FAST_OVF 1
+/* k_fast_strips' debug counters (plan->d_fs_cnt): FS_CNT_LINES lines of
+ * FS_CNT_STRIDE ints (128 B), a workgroup adds to line (strip + frame) mod
+ * FS_CNT_LINES; word 0 of a line: strips that took the dense (four-wave,
+ * row-mask) post-pass, word 1: strips whose corner list overflowed */
+#define FS_CNT_LINES 64
+#define FS_CNT_STRIDE 32
 #define ORBX_DEVERR_STEREO 4 /* the reference would index out of range / throw */
 #define ORBX_STEREO_MAXROWS 8192
 

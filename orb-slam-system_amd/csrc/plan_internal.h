@@ -35,6 +35,8 @@ struct orbx_plan {
   uint32_t* d_qperm = nullptr; /* per level: k_orient_brief's processing order (k_quadtree) */
   int32_t* d_qnode = nullptr;
   int *d_lcount = nullptr, *d_err = nullptr;
+  int* d_fs_cnt = nullptr; /* k_fast_strips' striped debug counters (FS_CNT_LINES x FS_CNT_STRIDE) */
+  long long fs_dense_total = 0, fs_ovf_total = 0; /* their sums since each was last read */
   int* h_err = nullptr; /* pinned: orbx_plan_check reads the error word without a blocking copy */
   size_t pyr_stride = 0, blur_stride = 0, slot_stride = 0, qk_stride = 0, qout_stride = 0;
   size_t qt_lds = 0;

@@ -43,7 +43,7 @@ assert KEYPOINT_DTYPE.itemsize == 28
 OK, ERR_ARG, ERR_CELL_ROI, ERR_LEVEL_SIZE, ERR_QUADTREE, ERR_CAPACITY, ERR_UNSUPPORTED, \
     ERR_HIP, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ORBM_PLAN_ZERO_TAIL, ORBM_PLAN_VALU = 1, 2  # orbm_plan_set_options flags (include/orbx.h)
-ORBX_PLAN_PYR_TILES, ORBX_PLAN_BRIEF_PATCH, ORBX_PLAN_BRIEF_LEVEL = 1, 8, 16  # orbx_plan_set_options flags
+ORBX_PLAN_PYR_TILES, ORBX_PLAN_BRIEF_PATCH, ORBX_PLAN_BRIEF_LEVEL, ORBX_PLAN_FAST_DENSE = 1, 8, 16, 64  # orbx_plan_set_options flags
 
 EXPORTED = [
     "orbx_abi_version", "orbx_status_string", "orbx_device_count", "orbx_tables",
@@ -52,7 +52,7 @@ EXPORTED = [
     "orbx_extractor_set_options", "orbx_extractor_level_host", "orbx_extractor_stats",
     "orbx_boundary_record_bytes", "orbx_boundary_pack", "orbx_boundary_unpack",
     "orbx_plan_create", "orbx_plan_destroy", "orbx_plan_geometry", "orbx_plan_extract",
-    "orbx_plan_check", "orbx_plan_debug_counters", "orbx_debug_set_fast_ccap", "orbx_plan_set_options", "orbx_plan_level", "orbx_stage_count", "orbx_stage_name", "orbx_plan_set_timing",
+    "orbx_plan_check", "orbx_plan_debug_counters", "orbx_plan_fast_dense_strips", "orbx_debug_set_fast_ccap", "orbx_plan_set_options", "orbx_plan_level", "orbx_stage_count", "orbx_stage_name", "orbx_plan_set_timing",
     "orbx_plan_stage_times", "orbx_synth_frames", "orbm_search_by_bow", "orbm_search_by_bow_kf_frame",
     "orbm_descriptor_distance_batch", "orbm_plan_create", "orbm_plan_destroy",
     "orbm_plan_match_frames", "orbm_plan_set_timing", "orbm_plan_stage_times", "orbm_plan_set_options",
@@ -151,6 +151,7 @@ _sig = {
     "orbx_plan_extract": (I, [P, P, I, SZ, SZ, P, P, P, P]),
     "orbx_plan_check": (I, [P, P]),
     "orbx_plan_debug_counters": (I, [P, P]),
+    "orbx_plan_fast_dense_strips": (I, [P, P]),
     "orbx_debug_set_fast_ccap": (I, [I]),
     "orbx_plan_set_options": (I, [P, I]),
     "orbx_plan_level": (I, [P, I, I, P, SZ, P, P, P]),
@@ -674,19 +675,25 @@ class Plan:
         _check(_lib.orbx_plan_check(self._h, _stream_handle(stream)), "orbx_plan_check")
 
     def debug_counters(self):
-        """{'fast_overflow_strips': n} since the last call (synchronises the plan's stream)"""
-        v = ctypes.c_int(0)
+        """{'fast_overflow_strips': n, 'fast_dense_strips': m} since the last
+        call (synchronises the plan's stream): FAST strips whose corner list
+        overflowed, and strips that took the dense post-pass"""
+        v, d = ctypes.c_int(0), ctypes.c_int(0)
         _check(_lib.orbx_plan_debug_counters(self._h, ctypes.byref(v)), "orbx_plan_debug_counters")
-        return {"fast_overflow_strips": v.value}
+        _check(_lib.orbx_plan_fast_dense_strips(self._h, ctypes.byref(d)), "orbx_plan_fast_dense_strips")
+        return {"fast_overflow_strips": v.value, "fast_dense_strips": d.value}
 
-    def set_options(self, pyramid="auto", brief="auto"):
+    def set_options(self, pyramid="auto", brief="auto", fast_post="auto"):
         """pyramid: 'auto' or 'tiles' (k_pyramid, the one pyramid path since
         the round-4 streaming kernels were retired); brief: 'auto' (the
         planner's choice), 'patch' (per-keypoint blur, k_orient_brief) or
         'level' (every level blurred once, k_blur + k_orient_brief_lb).
+        fast_post: 'auto' (FAST's post-pass chosen per strip by its corner
+        count) or 'dense' (every strip takes the four-wave row-mask form).
         Every combination gives the same results."""
         flags = {"auto": 0, "tiles": ORBX_PLAN_PYR_TILES}[pyramid]
         flags |= {"auto": 0, "patch": ORBX_PLAN_BRIEF_PATCH, "level": ORBX_PLAN_BRIEF_LEVEL}[brief]
+        flags |= {"auto": 0, "dense": ORBX_PLAN_FAST_DENSE}[fast_post]
         _check(_lib.orbx_plan_set_options(self._h, flags), "orbx_plan_set_options")
 
     def level(self, frame, lvl, stream=None):

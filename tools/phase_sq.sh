@@ -3,6 +3,16 @@
 #   VAR=new PHASES="1 5 2 3 0" WL=c4 bash tools/phase_sq.sh TAG
 # -> ${OUT_ROOT:-out}/phsq_TAG/v<phase>/run_counter_collection.csv; summarise with
 #    python3 tools/phase_sq_summary.py ${OUT_ROOT:-out}/phsq_TAG
+# Cut-offs 2 / 3 / 4 since the per-strip post-pass (round 7):
+#   2     every strip stops after the barrier that ends pass 1 (as before);
+#   3, 4  a dense strip (> 64 corners, or more than its list holds) stops after
+#         the NMS into the row masks, as before; a sparse strip (1..64 corners)
+#         stops once wave 0 has its lanes' two kept flags (its NMS: no ranks, no
+#         keys, no counts written); an empty strip has no NMS and no output
+#         phase: it writes its cells' zero counts and ends, at any cut-off > 2.
+#   So "3 - 2" is the NMS of dense strips + the kept flags of sparse ones + the
+#   zero counts of empty ones, and "0 - 3" the dense strips' mask output + the
+#   sparse strips' rank loop, key and count stores.
 set -o pipefail
 cd "$(git rev-parse --show-toplevel)"
 TAG=${1:-run}
