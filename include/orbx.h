@@ -25,8 +25,9 @@ extern "C" {
 /* 2 (round 6): plan option flags 2 and 4 retired (ORBX_ERR_ARG), flags 8 / 16,
  * orbx_proj_problem and the orbm_proj_plan_* / orbm_search_by_bow_kf_frame
  * entry points added (round 5).  orbx_tri_frame and
- * orbm_search_for_triangulation are additive (no existing struct or entry
- * point changes), so the version stays 2. */
+ * orbm_search_for_triangulation, and orbx_kf_frame / orbx_kf_query and
+ * orbm_keyframe_search, are additive (no existing struct or entry point
+ * changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
 /* status codes */
@@ -338,6 +339,51 @@ typedef struct {
 int orbm_search_for_triangulation(const orbx_tri_frame* kf1, int nkf2, const orbx_tri_frame* kf2,
                                   const float* F12, int only_stereo, int check_ori, int device,
                                   int32_t* match12, int* nmatches);
+
+/* One query of the keyframe window search below: the arguments of
+ * KeyFrame::GetFeaturesInArea and the octave gate of the loop after it. */
+typedef struct {
+  float x, y;      /* the u, v handed to KeyFrame::GetFeaturesInArea            */
+  float radius;    /* th * mvScaleFactors[level], already multiplied            */
+  int32_t level;   /* PredictScale(): candidates need level-1 <= octave <= level;
+                      < 0 = no octave gate                                      */
+  int32_t desc;    /* row of the call's descriptor pool                         */
+} orbx_kf_query;
+
+typedef struct {
+  int n;
+  const orbx_keypoint* keys;   /* mvKeysUn (pt and octave are read) */
+  const uint8_t* desc;         /* mDescriptors, n x 32              */
+  float min_x, min_y, grid_w_inv, grid_h_inv;  /* mnMinX, mnMinY, mfGridElement{Width,Height}Inv */
+} orbx_kf_frame;
+
+/* The search that ORBmatcher::Fuse(KF, vpMapPoints, th), Fuse(KF, Scw, ..)
+ * and SearchBySim3 share (src/ORBmatcher.cc:532-551, :600-619, :696-714),
+ * batched: problem p searches queries q[qoff[p] .. qoff[p+1]) in kf[p]; a
+ * query's descriptor is qdesc + 32 * q.desc, a pool of npool rows shared by
+ * every problem (in LocalMapping::SearchInNeighbors, src/LocalMapping.cc:
+ * 235-293, one map point's descriptor goes up once however many keyframes it
+ * is projected into).  One upload, one set of launches, one download.
+ * Per query j: KeyFrame::GetFeaturesInArea(x, y, radius) (src/KeyFrame.cc:
+ * 549-588: the 64 x 48 grid filled by PosInGrid's round() in index order, a
+ * feature outside the grid in no cell, the floor / ceil cell bounds with their
+ * clamps and early returns, cells visited ix then iy then the cell's list,
+ * the strict box test fabs(dx) < r && fabs(dy) < r), then over its result the
+ * gate level - 1 <= octave <= level and the first strict minimum of
+ * DescriptorDistance.  best_idx[j] = that feature's index or -1, best_dist[j]
+ * = its distance or INT_MAX (also where features were found but none passed
+ * the gate).  Ties go to the candidate visited first, which need not be the
+ * lowest index.  No threshold is applied (TH_LOW for Fuse, TH_HIGH for
+ * SearchBySim3 are the caller's), nothing is claimed: queries do not interact
+ * and several may return the same feature.  A float outside int's range
+ * converts to INT_MIN, as in the reference's x86 object.
+ * Host pointers; synchronous.  ORBX_ERR_ARG for nprob < 0, a qoff that does
+ * not start at 0 or decreases, a desc outside [0, npool), a non-finite x, y
+ * or radius (the reference would convert a NaN to int); ORBX_ERR_UNSUPPORTED
+ * for n > 8192.  nprob == 0, n == 0 and a problem without queries are valid. */
+int orbm_keyframe_search(int nprob, const orbx_kf_frame* kf, const orbx_kf_query* q,
+                         const int32_t* qoff /* nprob + 1 */, const uint8_t* qdesc, int npool,
+                         int device, int32_t* best_idx, int32_t* best_dist);
 
 /* ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:896-908), batched on the
  * device: dist[i] = Hamming(a + 32*ia[i], b + 32*ib[i]); host pointers. */

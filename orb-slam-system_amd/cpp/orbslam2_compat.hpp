@@ -14,11 +14,14 @@
 //     include/ORBextractor.h:25-91 (constructor, operator(), the six getters,
 //     public mvImagePyramid);
 //   * ORB_SLAM2::ORBmatcher with ORBmatcher.h's DescriptorDistance and the
-//     two SearchByBoW overloads (include/ORBmatcher.h:20-45) and
-//     SearchForTriangulation (:51-52) as templates over the caller's KeyFrame
-//     / MapPoint / Frame classes, reading exactly the members the reference
-//     reads (GetMapPointMatches, GetMapPoint, isBad, mvKeysUn, mFeatVec,
-//     mDescriptors, mvLevelSigma2, N).
+//     two SearchByBoW overloads (include/ORBmatcher.h:20-45),
+//     SearchForTriangulation (:51-52), SearchBySim3 (:56) and both Fuse forms
+//     (:59, :62) as templates over the caller's KeyFrame / MapPoint / Frame
+//     classes, reading exactly the members the reference reads
+//     (GetMapPointMatches, GetMapPoint, isBad, mvKeysUn, mFeatVec,
+//     mDescriptors, mvLevelSigma2, N; for Fuse / SearchBySim3 also the pose
+//     getters, fx .. cy, IsInImage, mvScaleFactors, the grid constants and
+//     the MapPoint members of src/ORBmatcher.cc:504-730).
 // A project that has OpenCV keeps its cv:: and uses INTEGRATION.md's glue
 // instead; define ORBX_COMPAT_NO_CV to take cv:: from OpenCV headers.
 #ifndef ORBX_ORBSLAM2_COMPAT_HPP
@@ -78,9 +81,14 @@ class Exception : public std::runtime_error {
 };
 
 // 2-D single-channel matrix header (CV_8UC1 images and descriptors; CV_32F for
-// the small float matrices the matcher takes, e.g. F12) over a shared byte
-// buffer (OpenCV value semantics: copies share data, create() reallocates
-// only when the shape changes)
+// the small float matrices the matcher takes, e.g. F12, and the poses and
+// points of Fuse / SearchBySim3) over a shared byte buffer (OpenCV value
+// semantics: copies share data, create() reallocates only when the shape
+// changes).  The CV_32F operators below (*, +, -, unary minus, t(), norm) are
+// plain float arithmetic in source order; their rounding against OpenCV's
+// small-matrix product (gemm, with its own accumulation order and a folded
+// scale) is unpinned, as DESIGN.md §11 says of undistortPoints: a code base
+// with OpenCV defines ORBX_COMPAT_NO_CV and gets OpenCV's rounding.
 class Mat {
  public:
   int rows = 0, cols = 0;
@@ -122,11 +130,29 @@ class Mat {
   T& at(int r, int c) { return ptr<T>(r)[c]; }
   template <typename T>
   const T& at(int r, int c) const { return ptr<T>(r)[c]; }
+  // at(i) of a row or column vector (Mat::at(int i0))
+  template <typename T>
+  T& at(int i) { return cols == 1 ? ptr<T>(i)[0] : ptr<T>(i / cols)[i % cols]; }
+  template <typename T>
+  const T& at(int i) const { return cols == 1 ? ptr<T>(i)[0] : ptr<T>(i / cols)[i % cols]; }
   Mat row(int r) const { return rowRange(r, r + 1); }
   Mat rowRange(int r0, int r1) const {
     Mat m(*this);
     m.rows = r1 - r0;
     m.data = data + (size_t)r0 * step;
+    return m;
+  }
+  Mat col(int c) const { return colRange(c, c + 1); }
+  Mat colRange(int c0, int c1) const {
+    Mat m(*this);
+    m.cols = c1 - c0;
+    m.data = data + (size_t)c0 * esz(type_);
+    return m;
+  }
+  Mat t() const {  // CV_32F
+    Mat m(cols, rows, type_);
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) m.at<float>(c, r) = at<float>(r, c);
     return m;
   }
   Mat clone() const {
@@ -146,6 +172,57 @@ class Mat {
   std::shared_ptr<std::vector<uint8_t>> buf_;
   int type_ = CV_8UC1;
 };
+
+// CV_32F arithmetic, float, in source order (see the note above class Mat)
+inline Mat operator*(const Mat& a, const Mat& b) {
+  if (a.cols != b.rows) throw Exception(-1, "cv::Mat operator*: shapes");
+  Mat m(a.rows, b.cols, CV_32F);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < b.cols; ++c) {
+      float acc = 0.0f;
+      for (int k = 0; k < a.cols; ++k) {
+        const float prod = a.at<float>(r, k) * b.at<float>(k, c);
+        acc = k == 0 ? prod : acc + prod;
+      }
+      m.at<float>(r, c) = acc;
+    }
+  return m;
+}
+inline Mat operator*(double s, const Mat& a) {
+  Mat m(a.rows, a.cols, CV_32F);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) m.at<float>(r, c) = (float)(s * (double)a.at<float>(r, c));
+  return m;
+}
+inline Mat operator*(const Mat& a, double s) { return s * a; }
+inline Mat operator+(const Mat& a, const Mat& b) {
+  if (a.rows != b.rows || a.cols != b.cols) throw Exception(-1, "cv::Mat operator+: shapes");
+  Mat m(a.rows, a.cols, CV_32F);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) m.at<float>(r, c) = a.at<float>(r, c) + b.at<float>(r, c);
+  return m;
+}
+inline Mat operator-(const Mat& a, const Mat& b) {
+  if (a.rows != b.rows || a.cols != b.cols) throw Exception(-1, "cv::Mat operator-: shapes");
+  Mat m(a.rows, a.cols, CV_32F);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) m.at<float>(r, c) = a.at<float>(r, c) - b.at<float>(r, c);
+  return m;
+}
+inline Mat operator-(const Mat& a) {
+  Mat m(a.rows, a.cols, CV_32F);
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) m.at<float>(r, c) = -a.at<float>(r, c);
+  return m;
+}
+// cv::norm(m), NORM_L2 of a CV_32F matrix: the squares summed in double, as
+// OpenCV's normL2 accumulates floats
+inline double norm(const Mat& a) {
+  double s = 0.0;
+  for (int r = 0; r < a.rows; ++r)
+    for (int c = 0; c < a.cols; ++c) s += (double)a.at<float>(r, c) * (double)a.at<float>(r, c);
+  return __builtin_sqrt(s);
+}
 
 class _InputArray {
  public:
@@ -291,9 +368,9 @@ class ORBextractor {
   std::vector<uint8_t> dbuf_;
 };
 
-// ORB_SLAM2::ORBmatcher: DescriptorDistance, SearchByBoW and
-// SearchForTriangulation (include/ORBmatcher.h:20-52;
-// src/ORBmatcher.cc:88-119,278-366,368-467,896-908).
+// ORB_SLAM2::ORBmatcher: DescriptorDistance, SearchByBoW,
+// SearchForTriangulation, SearchBySim3 and Fuse (include/ORBmatcher.h:20-62;
+// src/ORBmatcher.cc:88-119,278-366,368-467,504-730,896-908).
 class ORBmatcher {
  public:
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;  // ORBmatcher.cc:13-15
@@ -430,7 +507,250 @@ class ORBmatcher {
     return total;
   }
 
+  // Fuse(KeyFrame*, const vector<MapPoint*>&, th) (:504-568).  Three steps:
+  // the queries are built with the reference's own statements, one
+  // orbm_keyframe_search call finds every query's best feature, and the map
+  // points are walked in order with the reference's bookkeeping against live
+  // state (isBad / IsInKeyFrame re-tested at walk time, so a point an earlier
+  // entry of the list replaced or added is skipped as the reference skips it).
+  // Exact: within one call the only descriptors that change (Replace ->
+  // ComputeDistinctiveDescriptors) belong to map points already in pKF, and
+  // those are not queries.  KF: GetRotation / GetTranslation / GetCameraCenter,
+  // fx fy cx cy, IsInImage, mvScaleFactors, mvKeysUn, mDescriptors, N, mnMinX,
+  // mnMinY, mfGridElementWidthInv / HeightInv, GetMapPoint, AddMapPoint.  MP:
+  // isBad, IsInKeyFrame, GetWorldPos, Get{Min,Max}DistanceInvariance,
+  // PredictScale, GetDescriptor, Observations, Replace, AddObservation.
+  template <class KF, class MP>
+  int Fuse(KF* pKF, const std::vector<MP*>& vpMapPoints, const float th = 3.0) {
+    return Fuse(std::vector<KF*>(1, pKF), vpMapPoints, th);
+  }
+
+  // The first loop of LocalMapping::SearchInNeighbors (src/LocalMapping.cc:
+  // 255-260): Fuse(vpTargetKFs[p], vpMapPoints, th) for every target keyframe,
+  // as one device call; a map point's descriptor goes up once however many
+  // keyframes it projects into.  Returns the sum of the calls' return values.
+  // The walk is keyframe by keyframe, in order, against live state, but every
+  // query carries the map point's descriptor as it was when the call began: a
+  // map point that an earlier keyframe's Replace recomputed may match
+  // differently in a later keyframe than in the reference's loop
+  // (INTEGRATION.md 3e).  With one keyframe it is the reference's call, exact.
+  template <class KF, class MP>
+  int Fuse(const std::vector<KF*>& vpTargetKFs, const std::vector<MP*>& vpMapPoints, const float th = 3.0) {
+    KfSearch S;
+    std::vector<int32_t> slot(vpTargetKFs.size() * vpMapPoints.size(), -1);
+    for (size_t p = 0; p < vpTargetKFs.size(); ++p) {
+      KF* pKF = vpTargetKFs[p];
+      cv::Mat Rcw = pKF->GetRotation();
+      cv::Mat tcw = pKF->GetTranslation();
+      cv::Mat Ow = pKF->GetCameraCenter();
+      S.begin(pKF);
+      for (size_t i = 0; i < vpMapPoints.size(); ++i) {
+        MP* pMP = vpMapPoints[i];
+        if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+        slot[p * vpMapPoints.size() + i] = fuse_query(S, pKF, Rcw, tcw, Ow, pMP, th);
+      }
+      S.end();
+    }
+    S.run("Fuse");
+    int nFused = 0;
+    for (size_t p = 0; p < vpTargetKFs.size(); ++p) {
+      KF* pKF = vpTargetKFs[p];
+      for (size_t i = 0; i < vpMapPoints.size(); ++i) {
+        MP* pMP = vpMapPoints[i];
+        if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+        const int32_t j = slot[p * vpMapPoints.size() + i];
+        if (j < 0) continue;
+        const int bestDist = S.best_dist[j];
+        const int bestIdx = S.best_idx[j];
+        if (bestDist <= TH_LOW) {
+          MP* pMPinKF = pKF->GetMapPoint(bestIdx);
+          if (pMPinKF) {
+            if (!pMPinKF->isBad()) {
+              if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+            }
+          } else {
+            pMP->AddObservation(pKF, bestIdx);
+            pKF->AddMapPoint(pMP, bestIdx);
+          }
+          nFused++;
+        }
+      }
+    }
+    return nFused;
+  }
+
+  // Fuse(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>&, th, vpReplacePoint)
+  // (:570-634), LoopClosing::SearchAndFuse's form: the same three steps; the
+  // skip test is GetMapPoint(GetIndexInKeyFrame(pKF)), read as the reference
+  // reads it, and an occupied feature is reported in vpReplacePoint.  M: the
+  // caller's matrix type (cv::Mat, CV_32F).
+  template <class KF, class M, class MP>
+  int Fuse(KF* pKF, M Scw, const std::vector<MP*>& vpPoints, float th, std::vector<MP*>& vpReplacePoint) {
+    M Rcw = Scw.rowRange(0, 3).colRange(0, 3);
+    M tcw = Scw.rowRange(0, 3).col(3);
+    M Ow = -Rcw.t() * tcw;
+    KfSearch S;
+    std::vector<int32_t> slot(vpPoints.size(), -1);
+    S.begin(pKF);
+    for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
+      MP* pMP = vpPoints[iMP];
+      if (!pMP || pMP->isBad() || pKF->GetMapPoint(pMP->GetIndexInKeyFrame(pKF))) continue;
+      slot[iMP] = fuse_query(S, pKF, Rcw, tcw, Ow, pMP, th);
+    }
+    S.end();
+    S.run("Fuse");
+    int nFused = 0;
+    for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
+      MP* pMP = vpPoints[iMP];
+      if (!pMP || pMP->isBad() || pKF->GetMapPoint(pMP->GetIndexInKeyFrame(pKF))) continue;
+      if (slot[iMP] < 0) continue;
+      const int bestDist = S.best_dist[slot[iMP]];
+      const int bestIdx = S.best_idx[slot[iMP]];
+      if (bestDist <= TH_LOW) {
+        MP* pMPinKF = pKF->GetMapPoint(bestIdx);
+        if (pMPinKF) {
+          if (!pMPinKF->isBad()) vpReplacePoint[iMP] = pMPinKF;
+        } else {
+          pMP->AddObservation(pKF, bestIdx);
+          pKF->AddMapPoint(pMP, bestIdx);
+        }
+        nFused++;
+      }
+    }
+    return nFused;
+  }
+
+  // SearchBySim3 (:636-730; this reference searches one direction only, KF1's
+  // map points in KF2, and accepts at TH_HIGH).  Nothing changes during its
+  // loop, so the walk only fills vnMatch1.
+  template <class KF, class MP, class M>
+  int SearchBySim3(KF* pKF1, KF* pKF2, std::vector<MP*>& vpMatches12, const float& s12, const M& R12,
+                   const M& t12, const float th) {
+    const float& fx = pKF1->fx;
+    const float& fy = pKF1->fy;
+    const float& cx = pKF1->cx;
+    const float& cy = pKF1->cy;
+    M R1w = pKF1->GetRotation();
+    M t1w = pKF1->GetTranslation();
+    M sR21 = (1.0 / s12) * R12.t();
+    M t21 = -sR21 * t12;
+    const std::vector<MP*> vpMapPoints1 = pKF1->GetMapPointMatches();
+    // the reference indexes vbAlreadyMatched1 (this size) with vpMatches12's
+    if (vpMatches12.size() > vpMapPoints1.size()) orbx_throw(ORBX_ERR_ARG, "SearchBySim3");
+    std::vector<bool> vbAlreadyMatched1(vpMapPoints1.size(), false);
+    std::vector<int> vnMatch1(vpMapPoints1.size(), -1);
+    for (size_t i = 0; i < vpMatches12.size(); i++) {
+      MP* pMP = vpMatches12[i];
+      if (pMP) {
+        int idx2 = pMP->GetIndexInKeyFrame(pKF2);
+        if (idx2 >= 0) vbAlreadyMatched1[i] = true;
+      }
+    }
+    KfSearch S;
+    std::vector<int32_t> slot(vpMapPoints1.size(), -1);
+    S.begin(pKF2);
+    for (size_t i1 = 0; i1 < vpMapPoints1.size(); ++i1) {
+      MP* pMP1 = vpMapPoints1[i1];
+      if (!pMP1 || vbAlreadyMatched1[i1] || pMP1->isBad()) continue;
+      M p3Dw = pMP1->GetWorldPos();
+      M p3Dc1 = R1w * p3Dw + t1w;
+      M p3Dc2 = sR21 * p3Dc1 + t21;
+      if (p3Dc2.template at<float>(2) < 0.0f) continue;
+      float invz = 1.0f / p3Dc2.template at<float>(2);
+      float x = p3Dc2.template at<float>(0) * invz;
+      float y = p3Dc2.template at<float>(1) * invz;
+      float u = fx * x + cx;
+      float v = fy * y + cy;
+      if (!pKF2->IsInImage(u, v)) continue;
+      float dist = cv::norm(p3Dc2);
+      if (dist < pMP1->GetMinDistanceInvariance() || dist > pMP1->GetMaxDistanceInvariance()) continue;
+      int predictedLevel = pMP1->PredictScale(dist, pKF2);
+      float radius = th * pKF2->mvScaleFactors[predictedLevel];
+      slot[i1] = S.add(pMP1, u, v, radius, predictedLevel);
+    }
+    S.end();
+    S.run("SearchBySim3");
+    int nMatches = 0;
+    for (size_t i1 = 0; i1 < vpMapPoints1.size(); ++i1) {
+      if (slot[i1] < 0) continue;
+      if (S.best_dist[slot[i1]] <= TH_HIGH) {
+        vnMatch1[i1] = S.best_idx[slot[i1]];
+        nMatches++;
+      }
+    }
+    vpMatches12 = std::vector<MP*>(vpMapPoints1.size(), static_cast<MP*>(nullptr));
+    for (size_t i = 0; i < vnMatch1.size(); i++) {
+      if (vnMatch1[i] >= 0) vpMatches12[i] = pKF2->GetMapPoint(vnMatch1[i]);
+    }
+    return nMatches;
+  }
+
  protected:
+  // the queries of one orbm_keyframe_search call: begin(KF) .. add(..)* ..
+  // end() per problem, then run()
+  struct KfSearch {
+    std::vector<orbx_kf_frame> frames;
+    std::vector<orbx_kf_query> q;
+    std::vector<int32_t> qoff = std::vector<int32_t>(1, 0);
+    std::vector<uint8_t> pool;
+    std::map<const void*, int32_t> row;  // map point -> its pool row
+    std::vector<int32_t> best_idx, best_dist;
+
+    template <class KF>
+    void begin(KF* kf) {
+      orbx_kf_frame f;
+      f.n = kf->N;
+      f.keys = reinterpret_cast<const orbx_keypoint*>(kf->mvKeysUn.data());
+      f.desc = kf->mDescriptors.data;
+      f.min_x = kf->mnMinX;
+      f.min_y = kf->mnMinY;
+      f.grid_w_inv = kf->mfGridElementWidthInv;
+      f.grid_h_inv = kf->mfGridElementHeightInv;
+      frames.push_back(f);
+    }
+    void end() { qoff.push_back((int32_t)q.size()); }
+    // returns the query's index in best_idx / best_dist
+    template <class MP>
+    int32_t add(MP* pMP, float u, float v, float radius, int level) {
+      std::map<const void*, int32_t>::iterator it = row.find(pMP);
+      if (it == row.end()) {
+        const cv::Mat d = pMP->GetDescriptor();
+        it = row.insert(std::make_pair((const void*)pMP, (int32_t)(pool.size() / 32))).first;
+        pool.insert(pool.end(), d.ptr(0), d.ptr(0) + 32);
+      }
+      orbx_kf_query Q = {u, v, radius, level, it->second};
+      q.push_back(Q);
+      return (int32_t)q.size() - 1;
+    }
+    void run(const char* what) {
+      best_idx.assign(q.size() ? q.size() : 1, -1);
+      best_dist.assign(q.size() ? q.size() : 1, 0x7FFFFFFF);
+      orbx_throw(orbm_keyframe_search((int)frames.size(), frames.data(), q.data(), qoff.data(), pool.data(),
+                                      (int)(pool.size() / 32), 0, best_idx.data(), best_dist.data()),
+                 what);
+    }
+  };
+
+  // the projection statements both Fuse forms share (:514-531, :582-599);
+  // -1 where the reference `continue`s
+  template <class KF, class MP, class M>
+  static int32_t fuse_query(KfSearch& S, KF* pKF, const M& Rcw, const M& tcw, const M& Ow, MP* pMP, float th) {
+    M p3Dw = pMP->GetWorldPos();
+    M p3Dc = Rcw * p3Dw + tcw;
+    if (p3Dc.template at<float>(2) < 0.0f) return -1;
+    float invz = 1.0 / p3Dc.template at<float>(2);
+    float x = p3Dc.template at<float>(0) * invz;
+    float y = p3Dc.template at<float>(1) * invz;
+    float u = pKF->fx * x + pKF->cx;
+    float v = pKF->fy * y + pKF->cy;
+    if (!pKF->IsInImage(u, v)) return -1;
+    float dist = cv::norm(p3Dw - Ow);
+    if (dist < pMP->GetMinDistanceInvariance() || dist > pMP->GetMaxDistanceInvariance()) return -1;
+    int level = pMP->PredictScale(dist, pKF);
+    float radius = th * pKF->mvScaleFactors[level];
+    return S.add(pMP, u, v, radius, level);
+  }
+
   struct Flat {
     orbx_bow_frame f;
     std::vector<uint8_t> valid;

@@ -6,6 +6,7 @@ reference interfaces for tests and the benchmark:
   Extractor      ORB_SLAM2::ORBextractor  (/root/reference/include/ORBextractor.h:25-91)
   search_by_bow  ORBmatcher::SearchByBoW(KF, KF) (/root/reference/src/ORBmatcher.cc:278-366)
   search_for_triangulation  ORBmatcher::SearchForTriangulation, batched (ORBmatcher.cc:368-467)
+  keyframe_search  the search of ORBmatcher::Fuse / SearchBySim3, batched (ORBmatcher.cc:532-551)
   compute_stereo_matches  Frame::ComputeStereoMatches (/root/reference/src/Frame.cc:446-620)
   descriptor_distance_batch  ORBmatcher::DescriptorDistance (ORBmatcher.cc:896-908)
   Plan / MatchPlan  batched device-resident throughput path (bench.py)
@@ -62,7 +63,7 @@ EXPORTED = [
     "orbv_transform", "orbv_transform_batch", "orbv_check", "orbm_search_by_projection",
     "orbm_proj_plan_create", "orbm_proj_plan_destroy", "orbm_proj_plan_search",
     "orbm_compute_distinctive_descriptors", "orbx_undistort_keypoints", "orbx_selftest_sincos",
-    "orbx_selftest_sincos_range", "orbm_search_for_triangulation",
+    "orbx_selftest_sincos_range", "orbm_search_for_triangulation", "orbm_keyframe_search",
 ]
 
 
@@ -122,6 +123,25 @@ class TriFrame(ctypes.Structure):
                 ("level_sigma2", ctypes.c_void_p), ("nlevels", ctypes.c_int)]
 
 
+class KfFrame(ctypes.Structure):  # orbx_kf_frame
+    _fields_ = [("n", ctypes.c_int), ("keys", ctypes.c_void_p), ("desc", ctypes.c_void_p),
+                ("min_x", ctypes.c_float), ("min_y", ctypes.c_float),
+                ("grid_w_inv", ctypes.c_float), ("grid_h_inv", ctypes.c_float)]
+
+
+class KfQuery(ctypes.Structure):  # orbx_kf_query
+    _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("radius", ctypes.c_float),
+                ("level", ctypes.c_int32), ("desc", ctypes.c_int32)]
+
+
+KF_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("radius", "<f4"), ("level", "<i4"),
+                           ("desc", "<i4")])
+assert KF_QUERY_DTYPE.itemsize == ctypes.sizeof(KfQuery) == 20
+
+# k_kfwin_search's lanes per query and k_kfwin_grid's feature limit
+# (csrc/kfwin_internal.h)
+KFW_G, KFW_MAXN = 8, 8192
+
 # k_tri_search's tile (csrc/tri_internal.h): KF1 rows per wavefront and KF2
 # list entries staged in LDS at a time
 TRI_ROWS, TRI_CHUNK = 64, 64
@@ -163,6 +183,7 @@ _sig = {
     "orbm_search_by_bow": (I, [P, P, F, I, I, P, P]),
     "orbm_search_by_bow_kf_frame": (I, [P, P, F, I, I, P, P]),
     "orbm_search_for_triangulation": (I, [P, I, P, P, I, I, I, P, P]),
+    "orbm_keyframe_search": (I, [I, P, P, P, P, I, I, P, P]),
     "orbm_descriptor_distance_batch": (I, [P, I, P, I, P, P, I, I, P]),
     "orbm_plan_create": (I, [I, I, I, I, P]),
     "orbm_plan_destroy": (I, [P]),
@@ -512,6 +533,43 @@ def search_for_triangulation(kf1, kf2_list, F12_list, only_stereo=False, check_o
                                               1 if check_ori else 0, device, _p(m), _p(nm)),
            "orbm_search_for_triangulation")
     return m[:nk * b1.n].reshape(nk, b1.n).copy(), nm[:nk].copy()
+
+
+def kf_struct(k, keep):
+    """orbx_kf_frame of dict(keys, desc, min_x, min_y, grid_w_inv, grid_h_inv);
+    the arrays it points into are appended to keep."""
+    keys = np.ascontiguousarray(k["keys"], KEYPOINT_DTYPE)
+    desc = np.ascontiguousarray(k["desc"], np.uint8).reshape(-1, 32)
+    keep.extend([keys, desc])
+    return KfFrame(len(keys), _p(keys), _p(desc), k["min_x"], k["min_y"], k["grid_w_inv"],
+                   k["grid_h_inv"])
+
+
+def keyframe_search(kfs, queries, qdesc, device=0):
+    """The search ORBmatcher::Fuse (both forms) and SearchBySim3 share
+    (orbm_keyframe_search), batched: kfs[p] is a keyframe dict (kf_struct),
+    queries[p] its KF_QUERY_DTYPE array, qdesc the descriptor pool
+    (uint8[npool, 32]) the queries' desc rows index.  Returns a list of
+    (best_idx int32[nq_p], best_dist int32[nq_p]) per problem."""
+    if len(kfs) != len(queries):
+        raise OrbxError(ERR_ARG, "one query array per keyframe expected")
+    keep = []
+    nprob = len(kfs)
+    arr = (KfFrame * max(nprob, 1))()
+    for p, k in enumerate(kfs):
+        arr[p] = kf_struct(k, keep)
+    qs = [np.ascontiguousarray(q, KF_QUERY_DTYPE).reshape(-1) for q in queries]
+    qoff = np.zeros(nprob + 1, np.int32)
+    qoff[1:] = np.cumsum([len(q) for q in qs])
+    q = np.concatenate(qs) if qs else np.zeros(0, KF_QUERY_DTYPE)
+    q = np.ascontiguousarray(q, KF_QUERY_DTYPE)
+    qd = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
+    nq = int(qoff[-1])
+    bi = np.full(max(nq, 1), -7, np.int32)
+    bd = np.full(max(nq, 1), -7, np.int32)
+    _check(_lib.orbm_keyframe_search(nprob, ctypes.cast(arr, ctypes.c_void_p), _p(q), _p(qoff), _p(qd),
+                                     len(qd), device, _p(bi), _p(bd)), "orbm_keyframe_search")
+    return [(bi[qoff[p]:qoff[p + 1]].copy(), bd[qoff[p]:qoff[p + 1]].copy()) for p in range(nprob)]
 
 
 def descriptor_distance_batch(a, b, ia, ib, device=0):
