@@ -84,8 +84,7 @@ extern "C" int orbv_vocab_create(int k, int L, int scoring, int weighting, int n
   if (k < 0 || k > 20 || L < 1 || L > 10 || scoring < 0 || scoring > 5 || weighting < 0 ||
       weighting > 3 || nrec < 0 || (nrec > 0 && (!parent || !is_leaf || !desc || !weight)))
     return ORBX_ERR_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   const int n = nrec + 1;
   /* m_nodes[pid].children.push_back(nid) in record order; children of a
    * node stored contiguously (CSR) with their descriptors next to each other */

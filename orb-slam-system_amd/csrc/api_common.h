@@ -154,7 +154,7 @@ hipError_t stream_wait(hipStream_t s);
 int set_max_dynamic_lds(const void* kernel, int device);
 
 // a drop-in call's inputs [0, bytes) from its pinned staging buffer h into
-// its device arena d, on stream s: a kernel (k_stage_in) when
+// its device arena d, on stream s: a kernel (k_stage_in, kernels_misc.hip) when
 // ORBM_STAGE_KERNEL, else a DMA copy.  bytes: a multiple of 16 (Carve's
 // 256-byte blocks)
 int stage_in(void* d, const void* h, size_t bytes, hipStream_t s);
@@ -162,6 +162,20 @@ int stage_in(void* d, const void* h, size_t bytes, hipStream_t s);
 // staging h (device-accessible host memory): the copy kernel writing host
 // memory when ORBM_STAGE_KERNEL, else a DMA copy.  bytes: a multiple of 16
 int stage_out(void* h, const void* d, size_t bytes, hipStream_t s);
+// the tail of a drop-in call on workspace w: launch errors so far, the
+// results [out_begin, out_end) of the arena back into the staging buffer,
+// then the completion wait.  ORBX_OK or ORBX_ERR_HIP
+int finish_call(CallWs* w, size_t out_begin, size_t out_end);
+
+// ORBX_OK if `device` names a visible device, else ORBX_ERR_NO_DEVICE
+int check_device(int device);
+
+// a FeatureVector over n features (nnodes nodes, node j's features
+// feat[node_off[j] .. node_off[j + 1])): the three pointers non-null when
+// nnodes > 0, node_id strictly ascending (std::map keys), node_off
+// non-decreasing, every feat[i] < n.  ORBX_OK or ORBX_ERR_ARG
+int check_feature_vector(int n, int nnodes, const uint32_t* node_id, const uint32_t* node_off,
+                         const uint32_t* feat);
 
 }  // namespace orbx
 

@@ -38,9 +38,7 @@ extern "C" int orbm_keyframe_search(int nprob, const orbx_kf_frame* kf, const or
   }
   for (int p = 0; p < nprob; ++p)
     if (kf[p].n > KFW_MAXN) return ORBX_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   if (nq == 0) return ORBX_OK;  // nothing to write
   ORBX_TRY(hipSetDevice(device));
   WsLease L(device);
@@ -123,10 +121,8 @@ extern "C" int orbm_keyframe_search(int nprob, const orbx_kf_frame* kf, const or
                      reinterpret_cast<const int32_t*>(d + o_qoff),
                      reinterpret_cast<const int32_t*>(d + o_blk), d + o_pool, nq,
                      reinterpret_cast<int32_t*>(d + o_idx), reinterpret_cast<int32_t*>(d + o_dist));
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  rc = stage_out(h + in_end, d + in_end, out_end - in_end, s);
+  rc = finish_call(w, in_end, out_end);
   if (rc) return rc;
-  ORBX_TRY(stream_wait(s));
   memcpy(best_idx, h + o_idx, (size_t)nq * 4);
   memcpy(best_dist, h + o_dist, (size_t)nq * 4);
   return ORBX_OK;

@@ -13,8 +13,6 @@
 namespace orbx {
 __global__ void k_match_candidates(const MProblem*, const MNodePair*, int, int, uint2*, int4*,
                                    int2*);
-template <int NJ>
-__global__ void k_match_cand_lds(const MProblem*, const MNodePair*, uint2*, int4*, int2*);
 template <int NW>
 __global__ void k_match_cand_rows(const MProblem*, const MNodePair*, const uint4*, const uint32_t*,
                                   uint2*, int4*, int2*);
@@ -62,15 +60,7 @@ bool upper_bytes_zero(const uint8_t* d, int n) {
 int check_frame(const orbx_bow_frame* k) {
   if (!k || k->n < 0 || k->nnodes < 0) return ORBX_ERR_ARG;
   if (k->n > 0 && (!k->desc || !k->angle)) return ORBX_ERR_ARG;
-  if (k->nnodes > 0 && (!k->node_id || !k->node_off || !k->feat)) return ORBX_ERR_ARG;
-  for (int j = 0; j < k->nnodes; ++j) {
-    if (j > 0 && k->node_id[j] <= k->node_id[j - 1]) return ORBX_ERR_ARG; /* std::map keys */
-    if (k->node_off[j + 1] < k->node_off[j]) return ORBX_ERR_ARG;
-  }
-  const uint32_t nf = k->nnodes ? k->node_off[k->nnodes] : 0;
-  for (uint32_t i = 0; i < nf; ++i)
-    if (k->feat[i] >= (uint32_t)k->n) return ORBX_ERR_ARG;
-  return ORBX_OK;
+  return check_feature_vector(k->n, k->nnodes, k->node_id, k->node_off, k->feat);
 }
 
 void launch_match(const MProblem* d_probs, int nprob, const MNodePair* d_nps, int nnp, int nrows,
@@ -81,13 +71,16 @@ void launch_match(const MProblem* d_probs, int nprob, const MNodePair* d_nps, in
   {
     int dev = 0;
     hipGetDevice(&dev);
-    set_max_dynamic_lds((const void*)k_match_cand_lds<32>, dev);
     set_max_dynamic_lds((const void*)k_match_resolve_spec, dev);
     set_max_dynamic_lds((const void*)k_match_resolve, dev);
   }
   if (timer) timer->begin(ORBX_STAGE_MCAND, s);
   if (nrows > 0 && nnp > 0) {
-    if (max_n2 <= ORBM_MAX_N2 && nnp <= 65535 && d_gdesc2) {
+    // Candidates.  Both callers (bow_search, orbm_plan_match_frames) always
+    // pass d_gdesc2 and keep max_n2 <= ORBM_MAX_N2, so only the number of
+    // node pairs picks the path: the gather kernels take one grid.y row per
+    // node pair, and grid.y is bounded by 65535.
+    if (nnp <= 65535) {
       const bool mfma = ORBM_MFMA && d_gx2 && !d_gval2 && max_n2 > 0;
       if (mfma) {
         // distances on the matrix cores (no validity masks on this path):
@@ -139,12 +132,8 @@ void launch_match(const MProblem* d_probs, int nprob, const MNodePair* d_nps, in
           hipLaunchKernelGGL(k_match_cand_rows<8>, dim3((max_n1 + 127) / 128, nnp), dim3(256), 0, s,
                              d_probs, d_nps, d_gdesc2, d_gval2, d_cand, d_rowinfo, d_ev);
       }
-    } else if (max_n2 <= 64 * 32 && nnp <= 65535) {
-      // list2 staged in LDS, distances in registers (32 per lane)
-      const size_t lds = (size_t)std::max(max_n2, 1) * 32;
-      hipLaunchKernelGGL(k_match_cand_lds<32>, dim3((max_n1 + 63) / 64, nnp), dim3(256), lds, s,
-                         d_probs, d_nps, d_cand, d_rowinfo, d_ev);
     } else {
+      // more node pairs than grid.y holds: one wavefront per row, a flat grid
       hipLaunchKernelGGL(k_match_candidates, dim3((nrows + 3) / 4), dim3(256), 0, s, d_probs,
                          d_nps, nnp, nrows, d_cand, d_rowinfo, d_ev);
     }
@@ -189,9 +178,7 @@ static int bow_search(const orbx_bow_frame* kf1, const orbx_bow_frame* kf2, floa
   rc = check_frame(kf2);
   if (rc) return rc;
   if (kf2->n > ORBM_MAX_N2) return ORBX_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   // merge-join of the two FeatureVectors (ORBmatcher.cc:305-350): common
   // NodeIds in ascending order
   std::vector<MNodePair> nps;
@@ -313,10 +300,8 @@ static int bow_search(const orbx_bow_frame* kf1, const orbx_bow_frame* kf2, floa
                reinterpret_cast<int2*>(d + o_ev), reinterpret_cast<int*>(d + o_last),
                reinterpret_cast<const int*>(d + o_loff), s, nullptr,
                upper_bytes_zero(kf1->desc, kf1->n) && upper_bytes_zero(kf2->desc, kf2->n));
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  rc2 = stage_out(h + in_end, d + in_end, out_end - in_end, s);
+  rc2 = finish_call(w, in_end, out_end);
   if (rc2) return rc2;
-  ORBX_TRY(stream_wait(s));
   memcpy(match12, h + o_m12, n1 * 4);
   memcpy(nmatches, h + o_nm, sizeof(int));
   return ORBX_OK;
@@ -370,9 +355,7 @@ extern "C" int orbm_descriptor_distance_batch(const uint8_t* a, int na, const ui
   for (int i = 0; i < npairs; ++i)
     if (ia[i] < 0 || ia[i] >= na || ib[i] < 0 || ib[i] >= nb) return ORBX_ERR_ARG;
   if (npairs == 0) return ORBX_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
   WsLease L(device);
   CallWs* w = L.w;
@@ -396,10 +379,8 @@ extern "C" int orbm_descriptor_distance_batch(const uint8_t* a, int na, const ui
                      reinterpret_cast<const int32_t*>(d + o_ia),
                      reinterpret_cast<const int32_t*>(d + o_ib), npairs,
                      reinterpret_cast<int32_t*>(d + o_d));
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  rc = stage_out(h + o_d, d + o_d, out_end - o_d, s);
+  rc = finish_call(w, o_d, out_end);
   if (rc) return rc;
-  ORBX_TRY(stream_wait(s));
   memcpy(dist, h + o_d, (size_t)npairs * 4);
   return ORBX_OK;
 }
@@ -488,9 +469,7 @@ extern "C" int orbm_plan_create(int max_pairs, int kcap, int topn, int device, o
   if (!out || max_pairs < 1 || kcap < 1 || topn < 1 || topn > 0xFFFF || kcap > ORBM_MAX_N2)
     return ORBX_ERR_ARG;
   *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
   orbm_plan* m = new orbm_plan();
   m->device = device;

@@ -21,9 +21,8 @@ __global__ void k_boundary_copy(const uint8_t*, size_t, const uint8_t*, size_t, 
 
 using namespace orbx;
 
-static int check_device(int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ORBX_ERR_NO_DEVICE;
+static int select_device(int device) {
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   return hipSetDevice(device) == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
 }
 
@@ -35,7 +34,7 @@ extern "C" int orbm_compute_distinctive_descriptors(const uint8_t* desc, const i
   if (off[0] != 0 || total < 0 || (total > 0 && !desc)) return ORBX_ERR_ARG;
   for (int m = 0; m < nmp; ++m)
     if (off[m + 1] < off[m] || off[m + 1] - off[m] > (1 << 20)) return ORBX_ERR_ARG;
-  int rc = check_device(device);
+  int rc = select_device(device);
   if (rc) return rc;
   WsLease L(device);
   CallWs* w = L.w;
@@ -69,7 +68,7 @@ extern "C" int orbx_undistort_keypoints(const orbx_keypoint* kps, int n, const f
     memmove(out, kps, n * sizeof(orbx_keypoint));
     return ORBX_OK;
   }
-  int rc = check_device(device);
+  int rc = select_device(device);
   if (rc) return rc;
   UndistortArgs A;
   memset(&A, 0, sizeof(A));

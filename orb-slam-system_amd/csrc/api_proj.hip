@@ -79,8 +79,7 @@ extern "C" int orbm_search_by_projection(int mode, const orbx_proj_frame* F,
   if (n > PJ_MAXN) return ORBX_ERR_UNSUPPORTED;
   for (int i = 0; i < n; ++i) match[i] = -1;
   if (n == 0 || nq == 0) return ORBX_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
   WsLease L(device);
   CallWs* w = L.w;
@@ -125,9 +124,7 @@ extern "C" int orbm_search_by_projection(int mode, const orbx_proj_frame* F,
   hp->ncand = reinterpret_cast<int*>(d + o_nc);
   if (stage_in(d, h, in_end, s)) return ORBX_ERR_HIP;
   launch_proj(dp, 1, n, nq, mode, nnratio, th_dist, check_ori, s);
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  if (stage_out(h + in_end, d + in_end, out_end - in_end, s)) return ORBX_ERR_HIP;
-  ORBX_TRY(stream_wait(s));
+  if (finish_call(w, in_end, out_end)) return ORBX_ERR_HIP;
   memcpy(match, h + o_match, (size_t)n * 4);
   memcpy(nmatches, h + o_nm, sizeof(int));
   return ORBX_OK;
@@ -165,8 +162,7 @@ extern "C" int orbm_proj_plan_create(int max_problems, int max_n, int max_nq, in
   if (!out || max_problems < 1 || max_n < 1 || max_nq < 0) return ORBX_ERR_ARG;
   *out = nullptr;
   if (max_n > PJ_MAXN || max_problems > 65535) return ORBX_ERR_UNSUPPORTED;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
   orbm_proj_plan* p = new orbm_proj_plan();
   p->device = device;

@@ -25,14 +25,7 @@ namespace {
 int check_tri_frame(const orbx_tri_frame* k, bool kf2) {
   if (!k || k->n < 0 || k->nnodes < 0) return ORBX_ERR_ARG;
   if (k->n > 0 && (!k->keys || !k->desc)) return ORBX_ERR_ARG;
-  if (k->nnodes > 0 && (!k->node_id || !k->node_off || !k->feat)) return ORBX_ERR_ARG;
-  for (int j = 0; j < k->nnodes; ++j) {
-    if (j > 0 && k->node_id[j] <= k->node_id[j - 1]) return ORBX_ERR_ARG; /* std::map keys */
-    if (k->node_off[j + 1] < k->node_off[j]) return ORBX_ERR_ARG;
-  }
-  const uint32_t nf = k->nnodes ? k->node_off[k->nnodes] : 0;
-  for (uint32_t i = 0; i < nf; ++i)
-    if (k->feat[i] >= (uint32_t)k->n) return ORBX_ERR_ARG;
+  if (check_feature_vector(k->n, k->nnodes, k->node_id, k->node_off, k->feat)) return ORBX_ERR_ARG;
   if (kf2) {
     if (k->nlevels < 0 || (k->n > 0 && !k->level_sigma2)) return ORBX_ERR_ARG;
     for (int i = 0; i < k->n; ++i)
@@ -100,9 +93,7 @@ extern "C" int orbm_search_for_triangulation(const orbx_tri_frame* kf1, int nkf2
       seen[kf1->feat[j]] = 1;
     }
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return ORBX_ERR_NO_DEVICE;
+  if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   const size_t n1 = (size_t)kf1->n;
   // bOnlyStereo: `!bOnlyStereo && CheckDistEpipolarLine(..)` (:417) accepts
   // nothing in this reference, so there is nothing to launch
@@ -190,10 +181,8 @@ extern "C" int orbm_search_for_triangulation(const orbx_tri_frame* kf1, int nkf2
                        reinterpret_cast<const TriItem*>(d + o_items), f1, check_ori ? 1 : 0);
   hipLaunchKernelGGL(k_tri_finalize, dim3(nkf2), dim3(256), 0, s, d_probs, (int)n1,
                      check_ori ? 1 : 0);
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  rc = stage_out(h + in_end, d + in_end, out_end - in_end, s);
+  rc = finish_call(w, in_end, out_end);
   if (rc) return rc;
-  ORBX_TRY(stream_wait(s));
   memcpy(match12, h + o_m12, (size_t)nkf2 * n1 * 4);
   memcpy(nmatches, h + o_nm, (size_t)nkf2 * sizeof(int));
   return ORBX_OK;

@@ -110,7 +110,7 @@ hipError_t stream_wait(hipStream_t s) {
   }
 }
 
-__global__ void k_stage_in(uint4*, const uint4*, size_t);  // kernels_match.hip
+__global__ void k_stage_in(uint4*, const uint4*, size_t);  // kernels_misc.hip
 
 int stage_in(void* d, const void* h, size_t bytes, hipStream_t s) {
 #if ORBM_STAGE_KERNEL
@@ -136,6 +136,32 @@ int stage_out(void* h, const void* d, size_t bytes, hipStream_t s) {
 #else
   return hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, s) == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
 #endif
+}
+
+int finish_call(CallWs* w, size_t out_begin, size_t out_end) {
+  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
+  if (stage_out(w->h + out_begin, w->d + out_begin, out_end - out_begin, w->stream)) return ORBX_ERR_HIP;
+  return stream_wait(w->stream) == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
+}
+
+int check_device(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return ORBX_ERR_NO_DEVICE;
+  return ORBX_OK;
+}
+
+int check_feature_vector(int n, int nnodes, const uint32_t* node_id, const uint32_t* node_off,
+                         const uint32_t* feat) {
+  if (nnodes > 0 && (!node_id || !node_off || !feat)) return ORBX_ERR_ARG;
+  for (int j = 0; j < nnodes; ++j) {
+    if (j > 0 && node_id[j] <= node_id[j - 1]) return ORBX_ERR_ARG; /* std::map keys */
+    if (node_off[j + 1] < node_off[j]) return ORBX_ERR_ARG;
+  }
+  const uint32_t nf = nnodes ? node_off[nnodes] : 0;
+  for (uint32_t i = 0; i < nf; ++i)
+    if (feat[i] >= (uint32_t)n) return ORBX_ERR_ARG;
+  return ORBX_OK;
 }
 
 int set_max_dynamic_lds(const void* kernel, int device) {

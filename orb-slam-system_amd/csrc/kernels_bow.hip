@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "orbm_device.h"
 #include "wave_ops.h"
 
 namespace orbx {
@@ -50,9 +51,7 @@ __global__ __launch_bounds__(256) void k_bow_descend(
     for (int j = b + g; j < e; j += 16) {
       const uint4* cp = reinterpret_cast<const uint4*>(cdesc + (size_t)j * 32);
       const uint4 b0 = cp[0], b1 = cp[1];
-      const uint32_t d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) +
-                         __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
-                         __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+      const uint32_t d = ham256_popc(a0, a1, b0, b1);
       key = min(key, (d << 16) | (uint32_t)(j - b));
     }
 #pragma unroll

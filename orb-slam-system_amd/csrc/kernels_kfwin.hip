@@ -23,6 +23,7 @@
 
 #include "../../include/orbx.h"
 #include "kfwin_internal.h"
+#include "orbm_device.h"
 
 namespace orbx {
 
@@ -132,9 +133,7 @@ __global__ __launch_bounds__(KFW_BLOCK) void k_kfwin_search(
         const int octave = (int)h.w;
         if (Q.level >= 0 && (octave < Q.level - 1 || octave > Q.level)) continue;  // ORBmatcher.cc:542
         const uint4 b0 = rp[1], b1 = rp[2];
-        const uint32_t d = __popc(q0.x ^ b0.x) + __popc(q0.y ^ b0.y) + __popc(q0.z ^ b0.z) +
-                           __popc(q0.w ^ b0.w) + __popc(q1.x ^ b1.x) + __popc(q1.y ^ b1.y) +
-                           __popc(q1.z ^ b1.z) + __popc(q1.w ^ b1.w);
+        const uint32_t d = ham256_popc(q0, q1, b0, b1);
         best = min(best, (d << 16) | (uint32_t)j);  // rank j < KFW_MAXN, d <= 256
       }
     }

@@ -2,17 +2,27 @@
 // DescriptorDistance (src/ORBmatcher.cc:278-366, 469-502, 896-908).
 //
 // SearchByBoW is greedy and order dependent (vbMatched2 excludes KF2
-// features already taken by earlier KF1 features), so it is split into
-//   k_match_candidates  fully parallel: per KF1 feature ("row") the ORBM_T
-//                       best KF2 candidates by (distance, list position),
-//                       one wavefront per row, XOR + v_bcnt Hamming.
-//   k_match_resolve     the order-dependent part: one wavefront walks the
-//                       rows of a node pair in list order; each row is one
-//                       ballot over its candidates against an LDS bitmap of
-//                       taken KF2 features (exact fallback: full rescan).
-//                       Node pairs of a well-formed FeatureVector touch
-//                       disjoint KF2 features, so they run in parallel.
-//   k_match_finalize    rotation histogram + ComputeThreeMaxima + output.
+// features already taken by earlier KF1 features), so it runs as candidates
+// (parallel: per KF1 feature, "row", the ORBM_T best KF2 candidates by
+// (distance, list position)), then resolve (the order-dependent walk; node
+// pairs of a well-formed FeatureVector touch disjoint KF2 features and run
+// in parallel), then finalize.  Launched by launch_match (api_match.hip)
+// unless another launcher is named:
+//   k_match_select        batched plan only (orbm_plan_match_frames), before
+//                         launch_match: top-n keypoints of each frame
+//   k_match_expand2       candidates on the matrix cores (at most 65535 node
+//   k_match_cand_mfma     pairs, no validity arrays, ORBM_MFMA): list2 as
+//                         +-1 operands, then distances by MFMA
+//   k_match_gather2       candidates on the VALU (at most 65535 node pairs;
+//   k_match_cand_rows     validity arrays or ORBM_PLAN_VALU): list2 in node
+//                         order, then 128 rows per workgroup
+//   k_match_candidates    more than 65535 node pairs: one wavefront per row
+//   k_match_resolve_spec  resolve, 64 rows at a time speculatively: parallel
+//                         node pairs and at most 16384 KF2 features
+//   k_match_resolve       resolve otherwise (sequential problems, or a
+//                         vbMatched2 bitmap in dynamic LDS beyond 16384)
+//   k_match_finalize      rotation histogram + ComputeThreeMaxima + output
+//   k_hamming_pairs       orbm_descriptor_distance_batch
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -21,23 +31,10 @@
 
 #include "../../include/orbx.h"
 #include "match_internal.h"
+#include "orbm_device.h"
 #include "wave_ops.h"
 
 namespace orbx {
-
-__device__ __forceinline__ int hamming32(const uint32_t* a, const uint32_t* b) {
-  const uint4 a0 = reinterpret_cast<const uint4*>(a)[0], a1 = reinterpret_cast<const uint4*>(a)[1];
-  const uint4 b0 = reinterpret_cast<const uint4*>(b)[0], b1 = reinterpret_cast<const uint4*>(b)[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-__device__ __forceinline__ int hamming_u(const uint32_t d1[8], const uint32_t* b) {
-  const uint4 b0 = reinterpret_cast<const uint4*>(b)[0], b1 = reinterpret_cast<const uint4*>(b)[1];
-  return __popc(d1[0] ^ b0.x) + __popc(d1[1] ^ b0.y) + __popc(d1[2] ^ b0.z) +
-         __popc(d1[3] ^ b0.w) + __popc(d1[4] ^ b1.x) + __popc(d1[5] ^ b1.y) +
-         __popc(d1[6] ^ b1.z) + __popc(d1[7] ^ b1.w);
-}
 
 // a generic pointer known to point into global memory: loads through it are
 // global_load, which the wait counters order with the other vector memory
@@ -45,42 +42,7 @@ __device__ __forceinline__ int hamming_u(const uint32_t d1[8], const uint32_t* b
 // path makes the compiler wait for everything: vmcnt(0))
 typedef const uint32_t __attribute__((address_space(1)))* gu32_t;
 typedef const uint8_t __attribute__((address_space(1)))* gu8_t;
-__device__ __forceinline__ int hamming_g(const uint32_t d1[8], gu32_t b) {
-  int d = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) d += __popc(d1[k] ^ b[k]);  // two dwordx4 loads (32-B aligned rows)
-  return d;
-}
-
-// 256-bit Hamming distance as one accumulate chain: v_bcnt_u32_b32 adds its
-// second operand, so 8 xor + 8 bcnt (the compiler's add3 trees cost 3 more)
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
-  uint32_t r;
-  asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-  return r;
-}
-__device__ __forceinline__ uint32_t ham256(uint4 a0, uint4 a1, uint4 b0, uint4 b1) {
-  uint32_t d = bcnt_acc(a0.x ^ b0.x, 0u);
-  d = bcnt_acc(a0.y ^ b0.y, d);
-  d = bcnt_acc(a0.z ^ b0.z, d);
-  d = bcnt_acc(a0.w ^ b0.w, d);
-  d = bcnt_acc(a1.x ^ b1.x, d);
-  d = bcnt_acc(a1.y ^ b1.y, d);
-  d = bcnt_acc(a1.z ^ b1.z, d);
-  return bcnt_acc(a1.w ^ b1.w, d);
-}
-
 typedef uint32_t v4u_ __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t ham256v(uint4 a0, uint4 a1, v4u_ b0, v4u_ b1) {
-  uint32_t d = bcnt_acc(a0.x ^ b0.x, 0u);
-  d = bcnt_acc(a0.y ^ b0.y, d);
-  d = bcnt_acc(a0.z ^ b0.z, d);
-  d = bcnt_acc(a0.w ^ b0.w, d);
-  d = bcnt_acc(a1.x ^ b1.x, d);
-  d = bcnt_acc(a1.y ^ b1.y, d);
-  d = bcnt_acc(a1.z ^ b1.z, d);
-  return bcnt_acc(a1.w ^ b1.w, d);
-}
 
 __device__ __forceinline__ int find_node_pair(const MNodePair* nps, int nnp, int r) {
   int lo = 0, hi = nnp;  // last np with row_base <= r
@@ -122,7 +84,8 @@ __global__ __launch_bounds__(256) void k_match_candidates(
   for (int jj = lane; jj < NP.n2; jj += 64) {
     const int idx2 = (int)f2[jj];
     if (P.valid2 && !P.valid2[idx2]) continue;
-    const int d = hamming_u(d1, reinterpret_cast<const uint32_t*>(P.desc2 + (size_t)idx2 * 32));
+    const uint4* b = reinterpret_cast<const uint4*>(P.desc2 + (size_t)idx2 * 32);
+    const int d = ham256_popc(d1, b[0], b[1]);
     atomicAdd(&hist[wave][d], 1);
     ++nvalid;
   }
@@ -165,11 +128,15 @@ __global__ __launch_bounds__(256) void k_match_candidates(
   int nl = 0, ne = 0;
   for (int base = 0; base < NP.n2; base += 64) {
     const int jj = base + lane;
-    int d = 1 << 20;
+    // not a candidate (past the list, or invalid): above every D, the
+    // "take everything" D = 1 << 20 of a row with fewer than T candidates too
+    int d = INT_MAX;
     if (jj < NP.n2) {
       const int idx2 = (int)f2[jj];
-      if (!(P.valid2 && !P.valid2[idx2]))
-        d = hamming_u(d1, reinterpret_cast<const uint32_t*>(P.desc2 + (size_t)idx2 * 32));
+      if (!(P.valid2 && !P.valid2[idx2])) {
+        const uint4* b = reinterpret_cast<const uint4*>(P.desc2 + (size_t)idx2 * 32);
+        d = ham256_popc(d1, b[0], b[1]);
+      }
     }
     const uint64_t ml = __ballot(d < D), me = __ballot(d == D);
     const uint64_t below = (1ull << lane) - 1ull;
@@ -198,94 +165,6 @@ __global__ __launch_bounds__(256) void k_match_candidates(
   }
   if (lane == 0) rowinfo[r] = make_int4(1, nvalid, minD, idx1);
 }
-
-
-// ---------------------------------------------------------------------------
-// k_match_cand_lds: node pairs with n2 <= 64*NJ.  Workgroup = 64 rows of one
-// node pair; list2 descriptors staged once in LDS; every row's distances stay
-// in registers (NJ per lane).  rowinfo for every row; the sorted top-T
-// (dist<<16|pos, idx2) list only for rows whose best distance is < TH_LOW
-// (other rows can never be accepted and never change vbMatched2).
-// ---------------------------------------------------------------------------
-template <int NJ>
-__global__ __launch_bounds__(256) void k_match_cand_lds(
-    const MProblem* __restrict__ probs, const MNodePair* __restrict__ nps,
-    uint2* __restrict__ cand, int4* __restrict__ rowinfo, int2* __restrict__ ev) {
-  extern __shared__ uint4 sdesc[];  // 2 per list2 position
-  __shared__ uint32_t svalid[NJ * 2];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const MNodePair NP = nps[blockIdx.y];
-  const int a0 = blockIdx.x * 64;
-  if (a0 >= NP.n1) return;
-  const MProblem P = probs[NP.prob];
-  const uint32_t* f2 = P.feat2 + NP.off2;
-  const int n2 = NP.n2;
-  for (int i = tid; i < NJ * 2; i += 256) svalid[i] = 0u;
-  __syncthreads();
-  for (int i = tid; i < 2 * n2; i += 256) {
-    const uint32_t idx2 = f2[i >> 1];
-    sdesc[i] = reinterpret_cast<const uint4*>(P.desc2 + (size_t)idx2 * 32)[i & 1];
-    if ((i & 1) == 0 && !(P.valid2 && !P.valid2[idx2])) atomicOr(&svalid[(i >> 1) >> 5], 1u << ((i >> 1) & 31));
-  }
-  __syncthreads();
-  const int INF = 0x7FFF;
-  for (int rr = wave; rr < 64; rr += 4) {
-    const int a = a0 + rr;
-    if (a >= NP.n1) break;
-    const int r = NP.row_base + a;
-    if (lane == 0) ev[r] = make_int2(-1, 0);
-    const int idx1 = (int)P.feat1[NP.off1 + a];
-    if (P.valid1 && !P.valid1[idx1]) {
-      if (lane == 0) rowinfo[r] = make_int4(0, 0, 0, idx1);
-      continue;
-    }
-    const uint4 q0 = reinterpret_cast<const uint4*>(P.desc1 + (size_t)idx1 * 32)[0];
-    const uint4 q1 = reinterpret_cast<const uint4*>(P.desc1 + (size_t)idx1 * 32)[1];
-    int d[NJ];
-    int mn = INF, nv = 0;
-#pragma unroll
-    for (int i = 0; i < NJ; ++i) {
-      const int pos = lane + 64 * i;
-      int dd = INF;
-      if (pos < n2 && ((svalid[pos >> 5] >> (pos & 31)) & 1u)) {
-        const uint4 b0 = sdesc[2 * pos], b1 = sdesc[2 * pos + 1];
-        dd = __popc(q0.x ^ b0.x) + __popc(q0.y ^ b0.y) + __popc(q0.z ^ b0.z) + __popc(q0.w ^ b0.w) +
-             __popc(q1.x ^ b1.x) + __popc(q1.y ^ b1.y) + __popc(q1.z ^ b1.z) + __popc(q1.w ^ b1.w);
-        ++nv;
-      }
-      d[i] = dd;
-      mn = min(mn, dd);
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-      mn = min(mn, __shfl_xor(mn, s, 64));
-      nv += __shfl_xor(nv, s, 64);
-    }
-    if (lane == 0) rowinfo[r] = make_int4(1, nv, mn >= INF ? (1 << 20) : mn, idx1);
-    if (mn >= P.th_low) continue;
-    uint2* out = cand + (size_t)r * ORBM_T;
-    uint32_t key[NJ];
-#pragma unroll
-    for (int i = 0; i < NJ; ++i)
-      key[i] = d[i] < INF ? (((uint32_t)d[i] << 16) | (uint32_t)(lane + 64 * i)) : 0xFFFFFFFFu;
-    for (int t = 0; t < ORBM_T; ++t) {
-      uint32_t best = key[0];
-#pragma unroll
-      for (int i = 1; i < NJ; ++i) best = min(best, key[i]);
-#pragma unroll
-      for (int s = 32; s >= 1; s >>= 1) best = min(best, (uint32_t)__shfl_xor((int)best, s, 64));
-      if (lane == 0) out[t] = make_uint2(best, best != 0xFFFFFFFFu ? f2[best & 0xFFFFu] : 0u);
-      if (best == 0xFFFFFFFFu) {
-        if (lane > t && lane < ORBM_T) out[lane] = make_uint2(0xFFFFFFFFu, 0u);
-        break;
-      }
-#pragma unroll
-      for (int i = 0; i < NJ; ++i)
-        if (key[i] == best) key[i] = 0xFFFFFFFFu;
-    }
-  }
-}
-template __global__ void k_match_cand_lds<32>(const MProblem*, const MNodePair*, uint2*, int4*, int2*);
 
 
 // ---------------------------------------------------------------------------
@@ -1086,7 +965,8 @@ __global__ __launch_bounds__(256) void k_match_resolve(
             const int i2 = (int)f2[jj];
             if (P.valid2 && !P.valid2[i2]) continue;
             if ((bm[i2 >> 5] >> (i2 & 31)) & 1u) continue;
-            const int d = hamming_u(d1, reinterpret_cast<const uint32_t*>(P.desc2 + (size_t)i2 * 32));
+            const uint4* b = reinterpret_cast<const uint4*>(P.desc2 + (size_t)i2 * 32);
+            const int d = ham256_popc(d1, b[0], b[1]);
             best_merge(k1, d2, ((uint32_t)d << 16) | (uint32_t)jj, INT_MAX);
           }
 #pragma unroll
@@ -1302,7 +1182,7 @@ __global__ __launch_bounds__(64) void k_match_resolve_spec(
 #pragma unroll
             for (int u = 0; u < RS_RU; ++u) {
               const int jj = j0 + 64 * u + lane;
-              const int d = (int)ham256v(make_uint4(d1[0], d1[1], d1[2], d1[3]),
+              const int d = (int)ham256(make_uint4(d1[0], d1[1], d1[2], d1[3]),
                                          make_uint4(d1[4], d1[5], d1[6], d1[7]), da[u], db[u]);
               const bool ok = jj < NP.n2 && vv[u] && !((bm[i2[u] >> 5] >> (i2[u] & 31)) & 1u);
               if (ok) best_merge(kb, d2, ((uint32_t)d << 16) | (uint32_t)jj, INT_MAX);
@@ -1365,29 +1245,6 @@ __global__ __launch_bounds__(64) void k_match_resolve_spec(
 // ---------------------------------------------------------------------------
 // k_match_finalize: one workgroup per problem.
 // ---------------------------------------------------------------------------
-// ComputeThreeMaxima (ORBmatcher.cc:469-502), one thread
-__device__ __forceinline__ void three_maxima(const int* hist, int* ind) {
-  int ti[3] = {-1, -1, -1}, tv[3] = {0, 0, 0};
-  int hv[ORBM_HISTO];  // every bin read up front (independent LDS reads)
-#pragma unroll
-  for (int i = 0; i < ORBM_HISTO; ++i) hv[i] = hist[i];
-#pragma unroll
-  for (int i = 0; i < ORBM_HISTO; ++i) {
-    const int v = hv[i];
-    for (int jj = 0; jj < 3; ++jj) {
-      if (v > tv[jj]) {
-        for (int k = 2; k > jj; --k) { tv[k] = tv[k - 1]; ti[k] = ti[k - 1]; }
-        tv[jj] = v;
-        ti[jj] = i;
-        break;
-      }
-    }
-  }
-  if (tv[1] < 0.1f * tv[0]) { ti[1] = -1; ti[2] = -1; }
-  else if (tv[2] < 0.1f * tv[0]) { ti[2] = -1; }
-  ind[0] = ti[0]; ind[1] = ti[1]; ind[2] = ti[2];
-}
-
 __global__ __launch_bounds__(256) void k_match_finalize(const MProblem* __restrict__ probs,
                                                         const MNodePair* __restrict__ nps,
                                                         const int4* __restrict__ rowinfo,
@@ -1682,25 +1539,12 @@ __global__ __launch_bounds__(256) void k_match_select(
 }
 
 // DescriptorDistance over index pairs
-// ---------------------------------------------------------------------------
-// k_stage_in: a call's inputs from the pinned staging buffer (host memory the
-// GPU reads over PCIe) into its device arena, as a kernel on the call's
-// stream: the kernels after it start without the copy engine -> compute
-// queue handover a DMA copy needs (~8 us between the copy's end and the first
-// kernel in the drop-in SearchByBoW trace).  bytes: a multiple of 16.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_stage_in(uint4* __restrict__ d, const uint4* __restrict__ h,
-                                                  size_t n16) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) d[i] = h[i];
-}
-
 __global__ void k_hamming_pairs(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
                                 const int32_t* __restrict__ ia, const int32_t* __restrict__ ib,
                                 int npairs, int32_t* __restrict__ dist) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= npairs) return;
-  dist[i] = hamming32(reinterpret_cast<const uint32_t*>(a + (size_t)ia[i] * 32),
-                      reinterpret_cast<const uint32_t*>(b + (size_t)ib[i] * 32));
+  dist[i] = ham256_popc(a + (size_t)ia[i] * 32, b + (size_t)ib[i] * 32);
 }
 
 }  // namespace orbx

@@ -1,20 +1,14 @@
 // kernels_misc.hip -- gfx950 kernels of SURVEY.md §8f rank 4:
 //   MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:222-271) -> k_distinctive
 //   Frame::UndistortKeyPoints (src/Frame.cc:384-414, cv::undistortPoints) -> k_undistort
+// and the small utility kernels: k_boundary_copy, k_pack_results, k_stage_in
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/orbx.h"
+#include "orbm_device.h"
 
 namespace orbx {
-
-__device__ __forceinline__ int hamming32(const uint8_t* a, const uint8_t* b) {
-  const uint4* pa = reinterpret_cast<const uint4*>(a);
-  const uint4* pb = reinterpret_cast<const uint4*>(b);
-  const uint4 a0 = pa[0], a1 = pa[1], b0 = pb[0], b1 = pb[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // One wavefront per map point; lane = observation row i.  The median of row
 // i (nth_element at N/2 over the N distances, d_ii = 0 included) is the
@@ -41,7 +35,7 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t* __restrict__
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         int c = 0;
-        for (int j = 0; j < N; ++j) c += (j == i ? 0 : hamming32(D + (size_t)i * 32, D + (size_t)j * 32)) <= mid;
+        for (int j = 0; j < N; ++j) c += (j == i ? 0 : ham256_popc(D + (size_t)i * 32, D + (size_t)j * 32)) <= mid;
         if (c >= need) hi = mid; else lo = mid + 1;
       }
       bk = min(bk, ((uint32_t)lo << 20) | (uint32_t)i);
@@ -147,6 +141,18 @@ __global__ __launch_bounds__(256) void k_pack_results(const int* __restrict__ d_
   const int nk = (K * 28 + 15) >> 4, nd = K * 2;  // 16-B chunks: keypoint rows (7 dwords each), descriptors
   for (int i = tid; i < nk; i += nt) h_res[4 + i] = kps[i];
   for (int i = tid; i < nd; i += nt) h_res[desc_q16 + i] = desc[i];
+}
+
+// ---------------------------------------------------------------------------
+// k_stage_in: a call's inputs from the pinned staging buffer (host memory the
+// GPU reads over PCIe) into its device arena, as a kernel on the call's
+// stream: the kernels after it start without the copy engine -> compute
+// queue handover a DMA copy needs (~8 us between the copy's end and the first
+// kernel in the drop-in SearchByBoW trace).  bytes: a multiple of 16.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_stage_in(uint4* __restrict__ d, const uint4* __restrict__ h,
+                                                  size_t n16) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) d[i] = h[i];
 }
 
 }  // namespace orbx

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/orbx.h"
+#include "orbm_device.h"
 #include "wave_ops.h"
 
 namespace orbx {
@@ -144,9 +145,7 @@ __device__ __forceinline__ uint32_t proj_key(const orbx_query_proj& Q, const orb
   }
   const uint4* dp = reinterpret_cast<const uint4*>(desc + (size_t)idx * 32);
   const uint4 b0 = dp[0], b1 = dp[1];
-  const uint32_t d = __popc(q0.x ^ b0.x) + __popc(q0.y ^ b0.y) + __popc(q0.z ^ b0.z) +
-                     __popc(q0.w ^ b0.w) + __popc(q1.x ^ b1.x) + __popc(q1.y ^ b1.y) +
-                     __popc(q1.z ^ b1.z) + __popc(q1.w ^ b1.w);
+  const uint32_t d = ham256_popc(q0, q1, b0, b1);
   return (d << 16) | (uint32_t)rank;
 }
 
@@ -356,6 +355,9 @@ __global__ __launch_bounds__(64) void k_proj_resolve(const ProjProblem* __restri
   }
   if (mode != 1 && check_ori) {  // ComputeThreeMaxima (:469-502) + removal
     __syncthreads();
+    // not three_maxima of orbm_device.h on purpose: every lane of the walk's
+    // wave runs this, and the ladder stays in registers where the shared body
+    // (indexed ti / tv arrays) brings scratch into this kernel
     int ind1 = -1, ind2 = -1, ind3 = -1;
     int max1 = 0, max2 = 0, max3 = 0;
     for (int i = 0; i < 30; ++i) {

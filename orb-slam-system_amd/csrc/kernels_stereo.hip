@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/orbx.h"
+#include "orbm_device.h"
 #include "orbx_internal.h"
 #include "wave_ops.h"
 
@@ -198,9 +199,7 @@ __global__ __launch_bounds__(256) void k_stereo_match(
           if (oR >= levelL - 1 && oR <= levelL + 1 && uR >= minU && uR <= maxU) {
             const uint4* drp = reinterpret_cast<const uint4*>(DR + (size_t)iR * 32);
             const uint4 b0 = drp[0], b1 = drp[1];
-            const int dist = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) +
-                             __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) +
-                             __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+            const int dist = ham256_popc(a0, a1, b0, b1);
             const uint32_t key = ((uint32_t)dist << 16) | (uint32_t)iR;
             if (dist < 100 && key < best) {
               best = key;

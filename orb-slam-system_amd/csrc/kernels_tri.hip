@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "match_internal.h"
+#include "orbm_device.h"
 #include "tri_internal.h"
 
 namespace orbx {
@@ -106,9 +107,9 @@ __global__ __launch_bounds__(TRI_ROWS) void k_tri_search(const TriProblem* __res
       const int idx2 = __float_as_int(k2.w);
       if (idx2 < 0) continue;
       const uint4 lo = s_desc[j][0], hi = s_desc[j][1];
-      const int dist = __popc(d1[0] ^ lo.x) + __popc(d1[1] ^ lo.y) + __popc(d1[2] ^ lo.z) +
-                       __popc(d1[3] ^ lo.w) + __popc(d1[4] ^ hi.x) + __popc(d1[5] ^ hi.y) +
-                       __popc(d1[6] ^ hi.z) + __popc(d1[7] ^ hi.w);
+      // by value: handing the d1 array itself to a helper reorders this kernel's code
+      const int dist = ham256_popc(make_uint4(d1[0], d1[1], d1[2], d1[3]),
+                                   make_uint4(d1[4], d1[5], d1[6], d1[7]), lo, hi);
       if (dist > best_dist) continue;  // :414 (best_dist <= TH_LOW); equality goes on
       if (!tri_epipolar(a, b, c, den, k2.x, k2.y, s_thr[j])) continue;  // :417
       best_idx = idx2;
@@ -133,31 +134,6 @@ __global__ __launch_bounds__(TRI_ROWS) void k_tri_search(const TriProblem* __res
   if (lane < ORBM_HISTO && s_hist[lane]) atomicAdd(&P.hist[lane], s_hist[lane]);
 }
 
-// ComputeThreeMaxima (ORBmatcher.cc:469-502) over the bins' event counts, as
-// three_maxima of kernels_match.hip; returns the mask of the kept bins
-__device__ static uint32_t tri_kept_bins(const int* hist) {
-  int ti[3] = {-1, -1, -1}, tv[3] = {0, 0, 0};
-  for (int i = 0; i < ORBM_HISTO; ++i) {
-    const int v = hist[i];
-#pragma unroll
-    for (int jj = 0; jj < 3; ++jj) {
-      if (v > tv[jj]) {
-#pragma unroll
-        for (int k = 2; k > jj; --k) { tv[k] = tv[k - 1]; ti[k] = ti[k - 1]; }
-        tv[jj] = v;
-        ti[jj] = i;
-        break;
-      }
-    }
-  }
-  if (tv[1] < 0.1f * tv[0]) { ti[1] = -1; ti[2] = -1; }
-  else if (tv[2] < 0.1f * tv[0]) { ti[2] = -1; }
-  uint32_t keep = 0;
-  for (int j = 0; j < 3; ++j)
-    if (ti[j] >= 0) keep |= 1u << ti[j];
-  return keep;
-}
-
 __global__ __launch_bounds__(256) void k_tri_finalize(const TriProblem* __restrict__ probs, int n1,
                                                       int check_ori) {
   __shared__ uint32_t s_keep;
@@ -165,7 +141,13 @@ __global__ __launch_bounds__(256) void k_tri_finalize(const TriProblem* __restri
   const TriProblem& P = probs[blockIdx.x];
   const int tid = threadIdx.x;
   if (tid == 0) {
-    s_keep = check_ori ? tri_kept_bins(P.hist) : 0xFFFFFFFFu;
+    // the kept bins of ComputeThreeMaxima over the bins' event counts
+    s_keep = 0xFFFFFFFFu;
+    if (check_ori) {
+      int ind[3];
+      three_maxima(P.hist, ind);
+      s_keep = kept_bins_mask(ind);
+    }
     s_count = 0;
   }
   __syncthreads();

@@ -28,6 +28,13 @@ static void event(const char* fmt, long a, long b, long c) {
 namespace ORB_SLAM2 {
 class KeyFrame;
 
+// observations in keyframe-id order, not address order: Replace walks them,
+// and the order of its events must not depend on where the allocator put
+// each scene's keyframes
+struct KeyFrameById {
+  bool operator()(const KeyFrame* a, const KeyFrame* b) const;
+};
+
 class MapPoint {
  public:
   long id = 0;
@@ -35,7 +42,7 @@ class MapPoint {
   bool bad = false;
   int nObs = 0;
   float mfMinDistance = 0, mfMaxDistance = 0;
-  std::map<KeyFrame*, size_t> obs;
+  std::map<KeyFrame*, size_t, KeyFrameById> obs;
 
   bool isBad() { return bad; }
   bool IsInKeyFrame(KeyFrame* pKF) { return obs.count(pKF) != 0; }
@@ -120,6 +127,8 @@ class KeyFrame {
   }
 };
 
+inline bool KeyFrameById::operator()(const KeyFrame* a, const KeyFrame* b) const { return a->id < b->id; }
+
 inline int MapPoint::PredictScale(const float& currentDist, KeyFrame* pKF) {  // src/MapPoint.cc
   float ratio = mfMaxDistance / currentDist;
   int nScale = ceil(log(ratio) / pKF->mfLogScaleFactor);
@@ -138,7 +147,7 @@ inline void MapPoint::AddObservation(KeyFrame* pKF, size_t idx) {
 inline void MapPoint::Replace(MapPoint* pMP) {
   if (pMP->id == id) return;
   event("R %ld %ld %ld", id, pMP->id, 0);
-  std::map<KeyFrame*, size_t> o = obs;
+  std::map<KeyFrame*, size_t, KeyFrameById> o = obs;
   obs.clear();
   bad = true;
   for (auto& kv : o) {

@@ -634,3 +634,58 @@ def test_search_by_bow_complement_distances(gpu, oracle):
         rm, rnm = oracle.search_by_bow(kf1, kf2, ratio, False)
         assert nm == rnm and np.array_equal(m, rm), ratio
         assert nm > 0
+
+
+def _flip_bits(rng, base, flips):
+    """base with flips[i] distinct bits of row i flipped, by array operations
+    (bits start + k * step mod 256, step odd, k < flips[i])."""
+    n = len(base)
+    k = np.arange(int(flips.max()) if n else 0)
+    pos = (rng.integers(0, 256, n)[:, None] + k[None, :] * (2 * rng.integers(0, 128, n) + 1)[:, None]) % 256
+    bits = np.zeros((n, 256), np.uint8)
+    bits[np.arange(n)[:, None], pos] = k[None, :] < flips[:, None]
+    return base ^ np.packbits(bits, axis=1, bitorder="little")
+
+
+@pytest.fixture(scope="module")
+def many_nodes_bow():
+    """More than 65535 common nodes: feature i alone in node i on both sides,
+    so every node pair is one row and one candidate.  KF1 has 65536 + 64
+    features; KF2 has 65536, the most orbm_search_by_bow takes (beyond it the
+    call is ORBX_ERR_UNSUPPORTED), so KF1's last 64 nodes have no partner.
+    d2[i] = d1[i] with 0 / 5 / 30 / 49 / 50 / 51 / 60 bits flipped (TH_LOW is
+    50, exclusive); the rotations 0 / 30 / 60 / 90 degrees at about 4:3:2:1
+    fill four histogram bins, of which ComputeThreeMaxima drops the fourth."""
+    rng = np.random.default_rng(65600)
+    n1, n2 = 65536 + 64, 65536
+    d1 = rng.integers(0, 256, (n1, 32), dtype=np.uint8)
+    d2 = _flip_bits(rng, d1[:n2], np.array([0, 5, 30, 49, 50, 51, 60])[np.arange(n2) % 7])
+    ang1 = rng.uniform(0, 270, n1).astype(np.float32)
+    ang2 = ang1[:n2] + rng.choice(np.array([0, 30, 60, 90], np.float32), n2, p=[0.4, 0.3, 0.2, 0.1])
+    side = lambda d, a: dict(desc=d, angle=a, valid=None, node_id=np.arange(len(d), dtype=np.uint32),
+                             off=np.arange(len(d) + 1, dtype=np.uint32),
+                             feat=np.arange(len(d), dtype=np.uint32))
+    kf1, kf2 = side(d1, ang1), side(d2, ang2)
+    v1 = (rng.uniform(size=n1) > 0.1).astype(np.uint8)
+    v2 = (rng.uniform(size=n2) > 0.1).astype(np.uint8)
+    return kf1, kf2, v1, v2
+
+
+@pytest.mark.parametrize("masked", [False, True])
+def test_search_by_bow_many_node_pairs(gpu, oracle, many_nodes_bow, masked):
+    """65536 node pairs: more than one grid row per node pair can address, so
+    the candidates come from k_match_candidates (one wavefront per row), and
+    with more than 16384 KF2 features the walk is k_match_resolve with its
+    bitmap in dynamic LDS.  The oracle's result is checked first, alone: it
+    matches at least a quarter of the rows and the rotation check removes
+    some, so equality with it says something."""
+    kf1, kf2, v1, v2 = many_nodes_bow
+    if masked:
+        kf1, kf2 = dict(kf1, valid=v1), dict(kf2, valid=v2)
+    n = len(kf1["desc"])
+    rm, rnm = oracle.search_by_bow(kf1, kf2, 0.75, True)
+    assert rnm >= n // 4
+    assert oracle.search_by_bow(kf1, kf2, 0.75, False)[1] > rnm
+    m, nm = gpu.search_by_bow(kf1, kf2, 0.75, True)
+    assert nm == rnm
+    assert np.array_equal(m, rm)

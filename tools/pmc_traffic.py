@@ -27,7 +27,6 @@ STAGE_OF = {
     "k_match_setup": "match_select",
     "k_match_cand_rows": "match_candidates",
     "k_match_candidates": "match_candidates",
-    "k_match_cand_lds": "match_candidates",
     "k_match_cand_mfma": "match_candidates",
     "k_match_expand2": "match_candidates",
     "k_match_gather2": "match_candidates",
