@@ -105,6 +105,11 @@ struct StageTimer {
 // entry points stay re-entrant from the Tracking / LocalMapping /
 // LoopClosing threads) and returns it; steady-state calls do no hipMalloc,
 // hipFree or stream creation, and never synchronise the device.
+//
+// An entry point does not touch a workspace's buffers itself: it declares
+// typed slots on a CallArena (call_arena.h), which leases the workspace, lays
+// the slots out (inputs, outputs, scratch), sizes the buffers once, and does
+// the one upload (stage_in) and the one download (finish_call) below.
 // ---------------------------------------------------------------------------
 struct CallWs {
   int device = -1;
@@ -115,16 +120,6 @@ struct CallWs {
   size_t hcap = 0;
   // grow-only; a grow waits for this workspace's stream only
   int reserve(size_t dbytes, size_t hbytes);
-};
-
-// arena carving: 256-B aligned offsets
-struct Carve {
-  size_t off = 0;
-  size_t take(size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  }
 };
 
 CallWs* ws_acquire(int device);  // after hipSetDevice(device); nullptr on failure
@@ -155,8 +150,8 @@ int set_max_dynamic_lds(const void* kernel, int device);
 
 // a drop-in call's inputs [0, bytes) from its pinned staging buffer h into
 // its device arena d, on stream s: a kernel (k_stage_in, kernels_misc.hip) when
-// ORBM_STAGE_KERNEL, else a DMA copy.  bytes: a multiple of 16 (Carve's
-// 256-byte blocks)
+// ORBM_STAGE_KERNEL, else a DMA copy.  bytes: a multiple of 16 (CallArena's
+// 256-byte slots)
 int stage_in(void* d, const void* h, size_t bytes, hipStream_t s);
 // its results [.., + bytes) from the device arena d back into the pinned
 // staging h (device-accessible host memory): the copy kernel writing host
@@ -176,6 +171,40 @@ int check_device(int device);
 // non-decreasing, every feat[i] < n.  ORBX_OK or ORBX_ERR_ARG
 int check_feature_vector(int n, int nnodes, const uint32_t* node_id, const uint32_t* node_off,
                          const uint32_t* feat);
+
+// merge-join of two checked FeatureVectors (ORBmatcher.cc:305-350): calls
+// f(off1, n1, off2, n2), node j's list being feat[off .. off + n), for every
+// common NodeId in ascending order.  A non-zero return of f ends the walk and
+// is returned; otherwise ORBX_OK
+template <class F>
+int for_common_nodes(const uint32_t* id1, const uint32_t* off1, int nnodes1, const uint32_t* id2,
+                     const uint32_t* off2, int nnodes2, F&& f) {
+  for (int i = 0, j = 0; i < nnodes1 && j < nnodes2;) {
+    if (id1[i] < id2[j]) {
+      ++i;
+    } else if (id2[j] < id1[i]) {
+      ++j;
+    } else {
+      const int rc = f(off1[i], off1[i + 1] - off1[i], off2[j], off2[j + 1] - off2[j]);
+      if (rc) return rc;
+      ++i;
+      ++j;
+    }
+  }
+  return ORBX_OK;
+}
+
+// marks idx[0 .. count) in `seen` (one byte per feature): true if one of them
+// was marked before, by this call or an earlier one on the same table.  An
+// index past the table counts as a repeat (a caller that has not validated
+// the FeatureVector yet rejects both alike)
+inline bool index_repeats(std::vector<uint8_t>& seen, const uint32_t* idx, size_t count) {
+  for (size_t i = 0; i < count; ++i) {
+    if (idx[i] >= seen.size() || seen[idx[i]]) return true;
+    seen[idx[i]] = 1;
+  }
+  return false;
+}
 
 }  // namespace orbx
 

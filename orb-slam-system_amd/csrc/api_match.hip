@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
-#include "api_common.h"
+#include "call_arena.h"
 #include "match_internal.h"
 
 namespace orbx {
@@ -30,6 +30,9 @@ __global__ void k_match_resolve_spec(const MProblem*, const MNodePair*, int, con
                                      const int4*, int2*, int);
 __global__ void k_match_finalize(const MProblem*, const MNodePair*, const int4*, int2*, int*,
                                  const int*);
+__global__ void k_match_setup(MProblem*, MNodePair*, int, const orbx_keypoint*, const uint8_t*,
+                              const orbx_keypoint*, const uint8_t*, int, int, const uint32_t*, int32_t*,
+                              int*, float, int, int*);
 __global__ void k_match_select(MProblem*, MNodePair*, const orbx_keypoint*, const int*,
                                const orbx_keypoint*, const int*, int, int, uint32_t*);
 __global__ void k_hamming_pairs(const uint8_t*, const uint8_t*, const int32_t*, const int32_t*,
@@ -41,7 +44,6 @@ using namespace orbx;
 #ifndef ORBM_MFMA
 #define ORBM_MFMA 1 /* 0: VALU distances everywhere (profiling variant) */
 #endif
-
 
 namespace {
 
@@ -63,11 +65,26 @@ int check_frame(const orbx_bow_frame* k) {
   return check_feature_vector(k->n, k->nnodes, k->node_id, k->node_off, k->feat);
 }
 
-void launch_match(const MProblem* d_probs, int nprob, const MNodePair* d_nps, int nnp, int nrows,
-                  int sequential, int max_n1, int max_n2, int max_bitmap_n2, uint4* d_gdesc2,
-                  uint32_t* d_gval2, void* d_gx2, uint2* d_cand, int4* d_rowinfo, int2* d_ev,
-                  int* d_last, const int* d_last_off, hipStream_t s, StageTimer* timer,
-                  bool six_words) {
+// launch_match's device scratch, rows = list1 entries, g2 = list2 positions
+struct MatchScratch {
+  uint4* gdesc2 = nullptr;   // g2 x 2: list2 descriptors in node order
+  uint32_t* gval2 = nullptr; // g2: their validity, or nullptr (no masks)
+  void* gx2 = nullptr;       // g2 x 256 B: list2 as +-1 bytes, or nullptr (no MFMA path)
+  uint2* cand = nullptr;     // rows x ORBM_T
+  int4* rowinfo = nullptr;   // rows
+  int2* ev = nullptr;        // rows
+  int* last = nullptr;       // per KF1 feature
+  int* last_off = nullptr;   // per problem: its offset in last
+};
+
+// one launch's extent
+struct MatchShape {
+  int nprob, nnp, nrows, sequential, max_n1, max_n2, max_bitmap_n2;
+  bool six_words;
+};
+
+void launch_match(const MProblem* d_probs, const MNodePair* d_nps, const MatchShape& sh,
+                  const MatchScratch& sc, hipStream_t s, StageTimer* timer) {
   {
     int dev = 0;
     hipGetDevice(&dev);
@@ -75,45 +92,45 @@ void launch_match(const MProblem* d_probs, int nprob, const MNodePair* d_nps, in
     set_max_dynamic_lds((const void*)k_match_resolve, dev);
   }
   if (timer) timer->begin(ORBX_STAGE_MCAND, s);
-  if (nrows > 0 && nnp > 0) {
+  if (sh.nrows > 0 && sh.nnp > 0) {
     // Candidates.  Both callers (bow_search, orbm_plan_match_frames) always
-    // pass d_gdesc2 and keep max_n2 <= ORBM_MAX_N2, so only the number of
+    // pass gdesc2 and keep max_n2 <= ORBM_MAX_N2, so only the number of
     // node pairs picks the path: the gather kernels take one grid.y row per
     // node pair, and grid.y is bounded by 65535.
-    if (nnp <= 65535) {
-      const bool mfma = ORBM_MFMA && d_gx2 && !d_gval2 && max_n2 > 0;
+    if (sh.nnp <= 65535) {
+      const bool mfma = ORBM_MFMA && sc.gx2 && !sc.gval2 && sh.max_n2 > 0;
       if (mfma) {
         // distances on the matrix cores (no validity masks on this path):
         // list2 gathered straight into +-1 bytes
-        v4i_* gx2 = reinterpret_cast<v4i_*>(d_gx2);
+        v4i_* gx2 = static_cast<v4i_*>(sc.gx2);
         // a launch of fewer workgroups than CUs (one long node pair, e.g. a
         // drop-in call) splits each row tile's list 4 ways over a
         // workgroup's waves (MC_CSPLIT_WGS: below this many 128-row
         // workgroups; lists of 8+ tiles)
-        const bool csplit = (size_t)nnp * (size_t)((max_n1 + 128 * MC_RT - 1) / (128 * MC_RT)) < (size_t)MC_CSPLIT_WGS &&
-                            max_n2 >= 256;
-        const dim3 g1((max_n1 + 128 * MC_RT - 1) / (128 * MC_RT), nnp), g4((max_n1 + 31) / 32, nnp);
+        const bool csplit = (size_t)sh.nnp * (size_t)((sh.max_n1 + 128 * MC_RT - 1) / (128 * MC_RT)) < (size_t)MC_CSPLIT_WGS &&
+                            sh.max_n2 >= 256;
+        const dim3 g1((sh.max_n1 + 128 * MC_RT - 1) / (128 * MC_RT), sh.nnp), g4((sh.max_n1 + 31) / 32, sh.nnp);
 #define MC_LAUNCH(NK, PK)                                                                               \
   do {                                                                                                  \
     if (csplit)                                                                                         \
       hipLaunchKernelGGL((k_match_cand_mfma<NK, 1, PK, 4>), g4, dim3(256), 0, s, d_probs, d_nps, gx2,   \
-                         d_cand, d_rowinfo, d_ev);                                                      \
+                         sc.cand, sc.rowinfo, sc.ev);                                                \
     else                                                                                                \
       hipLaunchKernelGGL((k_match_cand_mfma<NK, MC_RT, PK, 1>), g1, dim3(256), 0, s, d_probs, d_nps,    \
-                         gx2, d_cand, d_rowinfo, d_ev);                                                 \
+                         gx2, sc.cand, sc.rowinfo, sc.ev);                                           \
   } while (0)
-        if (six_words) {
-          hipLaunchKernelGGL(k_match_expand2<6>, dim3((max_n2 * ORBM_EXPAND_PER_POS(6) + 255) / 256, nnp), dim3(256), 0, s,
+        if (sh.six_words) {
+          hipLaunchKernelGGL(k_match_expand2<6>, dim3((sh.max_n2 * ORBM_EXPAND_PER_POS(6) + 255) / 256, sh.nnp), dim3(256), 0, s,
                              d_probs, d_nps, gx2);
           // positions in the accumulator while they fit its 2^MC_PB(6) slots
-          if (ORBM_FP4 && MC_PK && max_n2 <= (1 << 14))
+          if (ORBM_FP4 && MC_PK && sh.max_n2 <= (1 << 14))
             MC_LAUNCH(6, ORBM_FP4 != 0);
           else
             MC_LAUNCH(6, false);
         } else {
-          hipLaunchKernelGGL(k_match_expand2<8>, dim3((max_n2 * ORBM_EXPAND_PER_POS(8) + 255) / 256, nnp), dim3(256), 0, s,
+          hipLaunchKernelGGL(k_match_expand2<8>, dim3((sh.max_n2 * ORBM_EXPAND_PER_POS(8) + 255) / 256, sh.nnp), dim3(256), 0, s,
                              d_probs, d_nps, gx2);
-          if (ORBM_FP4 && MC_PK && max_n2 <= (1 << 13))
+          if (ORBM_FP4 && MC_PK && sh.max_n2 <= (1 << 13))
             MC_LAUNCH(8, ORBM_FP4 != 0);
           else
             MC_LAUNCH(8, false);
@@ -122,48 +139,153 @@ void launch_match(const MProblem* d_probs, int nprob, const MNodePair* d_nps, in
       } else {
         // list2 descriptors gathered into node order, then two rows per lane,
         // the 4 waves splitting the positions; descriptors stream through LDS
-        if (max_n2 > 0)
-          hipLaunchKernelGGL(k_match_gather2, dim3((max_n2 + 127) / 128, nnp), dim3(256), 0, s, d_probs,
-                             d_nps, d_gdesc2, d_gval2);
-        if (six_words)
-          hipLaunchKernelGGL(k_match_cand_rows<6>, dim3((max_n1 + 127) / 128, nnp), dim3(256), 0, s,
-                             d_probs, d_nps, d_gdesc2, d_gval2, d_cand, d_rowinfo, d_ev);
+        if (sh.max_n2 > 0)
+          hipLaunchKernelGGL(k_match_gather2, dim3((sh.max_n2 + 127) / 128, sh.nnp), dim3(256), 0, s, d_probs,
+                             d_nps, sc.gdesc2, sc.gval2);
+        if (sh.six_words)
+          hipLaunchKernelGGL(k_match_cand_rows<6>, dim3((sh.max_n1 + 127) / 128, sh.nnp), dim3(256), 0, s,
+                             d_probs, d_nps, sc.gdesc2, sc.gval2, sc.cand, sc.rowinfo, sc.ev);
         else
-          hipLaunchKernelGGL(k_match_cand_rows<8>, dim3((max_n1 + 127) / 128, nnp), dim3(256), 0, s,
-                             d_probs, d_nps, d_gdesc2, d_gval2, d_cand, d_rowinfo, d_ev);
+          hipLaunchKernelGGL(k_match_cand_rows<8>, dim3((sh.max_n1 + 127) / 128, sh.nnp), dim3(256), 0, s,
+                             d_probs, d_nps, sc.gdesc2, sc.gval2, sc.cand, sc.rowinfo, sc.ev);
       }
     } else {
       // more node pairs than grid.y holds: one wavefront per row, a flat grid
-      hipLaunchKernelGGL(k_match_candidates, dim3((nrows + 3) / 4), dim3(256), 0, s, d_probs,
-                         d_nps, nnp, nrows, d_cand, d_rowinfo, d_ev);
+      hipLaunchKernelGGL(k_match_candidates, dim3((sh.nrows + 3) / 4), dim3(256), 0, s, d_probs,
+                         d_nps, sh.nnp, sh.nrows, sc.cand, sc.rowinfo, sc.ev);
     }
   }
   if (timer) timer->end(ORBX_STAGE_MCAND, s);
   if (timer) timer->begin(ORBX_STAGE_MRESOLVE, s);
-  const int units = sequential ? nprob : nnp;
-  if (nrows > 0 && units > 0 && !sequential && max_bitmap_n2 <= 16384) {
+  const int units = sh.sequential ? sh.nprob : sh.nnp;
+  if (sh.nrows > 0 && units > 0 && !sh.sequential && sh.max_bitmap_n2 <= 16384) {
     // speculative 64-row chunks; LDS = vbMatched2 bitmap + claim table
     // (+ alignment to 8 B) + the chunk's candidate slots (64 lanes x ORBM_T)
-    const int n2cap = std::max(max_bitmap_n2, 32);
+    const int n2cap = std::max(sh.max_bitmap_n2, 32);
     const size_t lds = (size_t)((((n2cap + 31) / 32 + n2cap) + 1) & ~1) * 4 + (size_t)64 * ORBM_T * sizeof(uint2);
     hipLaunchKernelGGL(k_match_resolve_spec, dim3(units), dim3(64), lds, s, d_probs, d_nps, units,
-                       d_cand, d_rowinfo, d_ev, n2cap);
-  } else if (nrows > 0 && units > 0) {
-    if (max_bitmap_n2 > 16384) {
-      const size_t lds = (size_t)((max_bitmap_n2 + 31) / 32) * 4;
+                       sc.cand, sc.rowinfo, sc.ev, n2cap);
+  } else if (sh.nrows > 0 && units > 0) {
+    if (sh.max_bitmap_n2 > 16384) {
+      const size_t lds = (size_t)((sh.max_bitmap_n2 + 31) / 32) * 4;
       hipLaunchKernelGGL(k_match_resolve, dim3(units), dim3(64), lds, s, d_probs, d_nps, units,
-                         sequential, d_cand, d_rowinfo, d_ev);
+                         sh.sequential, sc.cand, sc.rowinfo, sc.ev);
     } else {
       hipLaunchKernelGGL(k_match_resolve, dim3((units + 3) / 4), dim3(256), 0, s, d_probs, d_nps,
-                         units, sequential, d_cand, d_rowinfo, d_ev);
+                         units, sh.sequential, sc.cand, sc.rowinfo, sc.ev);
     }
   }
   if (timer) timer->end(ORBX_STAGE_MRESOLVE, s);
   if (timer) timer->begin(ORBX_STAGE_MFINAL, s);
-  hipLaunchKernelGGL(k_match_finalize, dim3(nprob), dim3(256), 0, s, d_probs, d_nps, d_rowinfo,
-                     d_ev, d_last, d_last_off);
+  hipLaunchKernelGGL(k_match_finalize, dim3(sh.nprob), dim3(256), 0, s, d_probs, d_nps, sc.rowinfo,
+                     sc.ev, sc.last, sc.last_off);
   if (timer) timer->end(ORBX_STAGE_MFINAL, s);
 }
+
+// the common nodes of two FeatureVectors as node pairs, ascending
+// (ORBmatcher.cc:305-350), with the totals the arena and the launch need
+struct NodePairs {
+  std::vector<MNodePair> nps;
+  int rows = 0, g2 = 0, max_n1 = 0, max_n2 = 0;
+};
+
+int node_pair_table(const orbx_bow_frame* kf1, const orbx_bow_frame* kf2, NodePairs& T) {
+  return for_common_nodes(
+      kf1->node_id, kf1->node_off, kf1->nnodes, kf2->node_id, kf2->node_off, kf2->nnodes,
+      [&](uint32_t off1, uint32_t n1, uint32_t off2, uint32_t n2) {
+        if (n2 > 0xFFFF) return ORBX_ERR_UNSUPPORTED; /* 16-bit list positions */
+        const MNodePair np = {0, (int)off1, (int)n1, (int)off2, (int)n2, T.rows, T.g2};
+        T.rows += np.n1;
+        T.g2 += np.n2;
+        T.max_n1 = std::max(T.max_n1, np.n1);
+        T.max_n2 = std::max(T.max_n2, np.n2);
+        T.nps.push_back(np);
+        return ORBX_OK;
+      });
+}
+
+// node pairs may run in parallel iff no KF2 feature appears in two of them
+int needs_sequential(const orbx_bow_frame* kf2, const NodePairs& T) {
+  std::vector<uint8_t> seen((size_t)kf2->n, 0);
+  for (const MNodePair& np : T.nps)
+    if (index_repeats(seen, kf2->feat + np.off2, (size_t)np.n2)) return 1;
+  return 0;
+}
+
+// one search's arena: the two frames, the problem and node-pair tables, the
+// results, launch_match's scratch
+struct BowSlots {
+  Slot<uint8_t> desc1, desc2, val1, val2, gx2;
+  Slot<float> ang1, ang2;
+  Slot<uint32_t> feat1, feat2, gval2;
+  Slot<MProblem> prob;
+  Slot<MNodePair> nps;
+  Slot<int32_t> m12;
+  Slot<int> loff, nm, last;
+  Slot<uint2> cand;
+  Slot<int4> rowinfo;
+  Slot<int2> ev;
+  Slot<uint4> gdesc2;
+
+  BowSlots(CallArena& A, const orbx_bow_frame* kf1, const orbx_bow_frame* kf2, const NodePairs& T,
+           int32_t* match12, int* nmatches) {
+    const size_t n1 = (size_t)kf1->n, n2 = (size_t)kf2->n, rows = (size_t)T.rows, g2 = (size_t)T.g2;
+    desc1 = A.in(kf1->desc, n1 * 32);
+    desc2 = A.in(kf2->desc, n2 * 32);
+    ang1 = A.in(kf1->angle, n1);
+    ang2 = A.in(kf2->angle, n2);
+    val1 = A.in_opt(kf1->valid, n1);
+    val2 = A.in_opt(kf2->valid, n2);
+    feat1 = A.in(kf1->feat, kf1->nnodes ? kf1->node_off[kf1->nnodes] : 0);
+    feat2 = A.in(kf2->feat, kf2->nnodes ? kf2->node_off[kf2->nnodes] : 0);
+    prob = A.in<MProblem>(1);
+    nps = A.in(T.nps.data(), T.nps.size());
+    loff = A.in<int>(1);
+    m12 = A.out(match12, n1);
+    nm = A.out(nmatches, 1);
+    cand = A.scratch<uint2>(rows * ORBM_T);
+    rowinfo = A.scratch<int4>(rows);
+    ev = A.scratch<int2>(rows);
+    last = A.scratch<int>(n1);
+    gdesc2 = A.scratch<uint4>(g2 * 2);
+    // validity masks take the VALU path, no masks the MFMA path's +-1 bytes
+    if (kf2->valid) gval2 = A.scratch<uint32_t>(g2);
+    else gx2 = A.scratch<uint8_t>(g2 * 256);
+  }
+
+  // the problem table's one entry and last's offset, built in staging
+  void fill(const CallArena& A, const orbx_bow_frame* kf1, const orbx_bow_frame* kf2,
+            const NodePairs& T, float nnratio, int check_ori, int sequential, int th_low) const {
+    MProblem P = {};  // np_begin = row_begin = 0: the one problem owns every node pair and row
+    P.desc1 = A.d(desc1);
+    P.desc2 = A.d(desc2);
+    P.ang1 = A.d(ang1);
+    P.ang2 = A.d(ang2);
+    P.valid1 = A.d(val1);
+    P.valid2 = A.d(val2);
+    P.feat1 = A.d(feat1);
+    P.feat2 = A.d(feat2);
+    P.match12 = A.d(m12);
+    P.nmatches = A.d(nm);
+    P.ang_stride = 1;
+    P.n1 = kf1->n;
+    P.n2 = kf2->n;
+    P.np_end = (int)T.nps.size();
+    P.row_end = T.rows;
+    P.check_ori = check_ori ? 1 : 0;
+    P.nnratio = nnratio;
+    P.sequential = sequential;
+    P.dcap = orbm_dcap(nnratio, th_low);
+    P.th_low = th_low;
+    *A.h(prob) = P;
+    *A.h(loff) = 0;
+  }
+
+  MatchScratch scratch(const CallArena& A) const {
+    return MatchScratch{A.d(gdesc2), A.d(gval2), A.d(gx2),  A.d(cand),
+                        A.d(rowinfo), A.d(ev),   A.d(last), A.d(loff)};
+  }
+};
 
 }  // namespace
 
@@ -179,132 +301,27 @@ static int bow_search(const orbx_bow_frame* kf1, const orbx_bow_frame* kf2, floa
   if (rc) return rc;
   if (kf2->n > ORBM_MAX_N2) return ORBX_ERR_UNSUPPORTED;
   if (check_device(device)) return ORBX_ERR_NO_DEVICE;
-  // merge-join of the two FeatureVectors (ORBmatcher.cc:305-350): common
-  // NodeIds in ascending order
-  std::vector<MNodePair> nps;
-  int rows = 0, max_n1 = 0, max_n2 = 0, g2 = 0;
-  {
-    int f1 = 0, f2 = 0;
-    while (f1 < kf1->nnodes && f2 < kf2->nnodes) {
-      const uint32_t a = kf1->node_id[f1], b = kf2->node_id[f2];
-      if (a == b) {
-        MNodePair np;
-        np.prob = 0;
-        np.off1 = (int)kf1->node_off[f1];
-        np.n1 = (int)(kf1->node_off[f1 + 1] - kf1->node_off[f1]);
-        np.off2 = (int)kf2->node_off[f2];
-        np.n2 = (int)(kf2->node_off[f2 + 1] - kf2->node_off[f2]);
-        if (np.n2 > 0xFFFF) return ORBX_ERR_UNSUPPORTED; /* 16-bit list positions */
-        np.row_base = rows;
-        np.g2 = g2;
-        rows += np.n1;
-        g2 += np.n2;
-        max_n1 = std::max(max_n1, np.n1);
-        max_n2 = std::max(max_n2, np.n2);
-        nps.push_back(np);
-        ++f1;
-        ++f2;
-      } else if (a < b) {
-        ++f1;
-      } else {
-        ++f2;
-      }
-    }
-  }
-  // node pairs may run in parallel iff no KF2 feature appears in two of them
-  int sequential = 0;
-  {
-    std::vector<uint8_t> seen(kf2->n > 0 ? kf2->n : 1, 0);
-    for (const MNodePair& np : nps)
-      for (int i = 0; i < np.n2 && !sequential; ++i) {
-        const uint32_t f = kf2->feat[np.off2 + i];
-        if (seen[f]) sequential = 1;
-        seen[f] = 1;
-      }
-  }
+  NodePairs T;
+  rc = node_pair_table(kf1, kf2, T);
+  if (rc) return rc;
+  const int sequential = needs_sequential(kf2, T);
   if (kf1->n == 0) {
     *nmatches = 0;
     return ORBX_OK;
   }
   ORBX_TRY(hipSetDevice(device));
-  WsLease L(device);
-  CallWs* w = L.w;
-  if (!w) return ORBX_ERR_HIP;
-  hipStream_t s = w->stream;
-  // one arena: inputs [0, in_end) go up in one copy from pinned staging,
-  // outputs [in_end, out_end) come back in one copy, scratch after them
-  const uint32_t nf1 = kf1->nnodes ? kf1->node_off[kf1->nnodes] : 0;
-  const uint32_t nf2 = kf2->nnodes ? kf2->node_off[kf2->nnodes] : 0;
-  const size_t n1 = (size_t)kf1->n, n2 = (size_t)kf2->n, nnp = nps.size();
-  Carve C;
-  const size_t o_desc1 = C.take(n1 * 32), o_desc2 = C.take(n2 * 32);
-  const size_t o_ang1 = C.take(n1 * 4), o_ang2 = C.take(n2 * 4);
-  const size_t o_val1 = kf1->valid ? C.take(n1) : 0, o_val2 = kf2->valid ? C.take(n2) : 0;
-  const size_t o_feat1 = C.take((size_t)nf1 * 4), o_feat2 = C.take((size_t)nf2 * 4);
-  const size_t o_prob = C.take(sizeof(MProblem)), o_nps = C.take(nnp * sizeof(MNodePair));
-  const size_t o_loff = C.take(sizeof(int));
-  const size_t in_end = C.off;
-  const size_t o_m12 = C.take(n1 * 4), o_nm = C.take(sizeof(int));
-  const size_t out_end = C.off;
-  const size_t o_cand = C.take((size_t)rows * ORBM_T * sizeof(uint2));
-  const size_t o_rowinfo = C.take((size_t)rows * sizeof(int4)), o_ev = C.take((size_t)rows * sizeof(int2));
-  const size_t o_last = C.take(n1 * 4), o_g2 = C.take((size_t)g2 * 2 * sizeof(uint4));
-  const size_t o_gv2 = kf2->valid ? C.take((size_t)g2 * 4) : 0;
-  const size_t o_gx2 = kf2->valid ? 0 : C.take((size_t)g2 * 256);  /* +-1 bytes for the MFMA path */
-  int rc2 = w->reserve(C.off, out_end);
-  if (rc2) return rc2;
-  uint8_t* d = w->d;
-  uint8_t* h = w->h;
-  memcpy(h + o_desc1, kf1->desc, n1 * 32);
-  memcpy(h + o_desc2, kf2->desc, n2 * 32);
-  memcpy(h + o_ang1, kf1->angle, n1 * 4);
-  memcpy(h + o_ang2, kf2->angle, n2 * 4);
-  if (kf1->valid) memcpy(h + o_val1, kf1->valid, n1);
-  if (kf2->valid) memcpy(h + o_val2, kf2->valid, n2);
-  if (nf1) memcpy(h + o_feat1, kf1->feat, (size_t)nf1 * 4);
-  if (nf2) memcpy(h + o_feat2, kf2->feat, (size_t)nf2 * 4);
-  MProblem P;
-  memset(&P, 0, sizeof(P));
-  P.desc1 = d + o_desc1;
-  P.desc2 = d + o_desc2;
-  P.ang1 = reinterpret_cast<const float*>(d + o_ang1);
-  P.ang2 = reinterpret_cast<const float*>(d + o_ang2);
-  P.valid1 = kf1->valid ? d + o_val1 : nullptr;
-  P.valid2 = kf2->valid ? d + o_val2 : nullptr;
-  P.feat1 = reinterpret_cast<const uint32_t*>(d + o_feat1);
-  P.feat2 = reinterpret_cast<const uint32_t*>(d + o_feat2);
-  P.match12 = reinterpret_cast<int32_t*>(d + o_m12);
-  P.nmatches = reinterpret_cast<int*>(d + o_nm);
-  P.ang_stride = 1;
-  P.n1 = kf1->n;
-  P.n2 = kf2->n;
-  P.np_begin = 0;
-  P.np_end = (int)nnp;
-  P.row_begin = 0;
-  P.row_end = rows;
-  P.check_ori = check_ori ? 1 : 0;
-  P.nnratio = nnratio;
-  P.sequential = sequential;
-  P.dcap = orbm_dcap(nnratio, th_low);
-  P.th_low = th_low;
-  memcpy(h + o_prob, &P, sizeof(P));
-  if (nnp) memcpy(h + o_nps, nps.data(), nnp * sizeof(MNodePair));
-  memset(h + o_loff, 0, sizeof(int));
-  rc2 = stage_in(d, h, in_end, s);
-  if (rc2) return rc2;
-  launch_match(reinterpret_cast<MProblem*>(d + o_prob), 1, reinterpret_cast<MNodePair*>(d + o_nps),
-               (int)nnp, rows, sequential, max_n1, max_n2, kf2->n,
-               reinterpret_cast<uint4*>(d + o_g2),
-               kf2->valid ? reinterpret_cast<uint32_t*>(d + o_gv2) : nullptr,
-               kf2->valid ? nullptr : d + o_gx2, reinterpret_cast<uint2*>(d + o_cand), reinterpret_cast<int4*>(d + o_rowinfo),
-               reinterpret_cast<int2*>(d + o_ev), reinterpret_cast<int*>(d + o_last),
-               reinterpret_cast<const int*>(d + o_loff), s, nullptr,
-               upper_bytes_zero(kf1->desc, kf1->n) && upper_bytes_zero(kf2->desc, kf2->n));
-  rc2 = finish_call(w, in_end, out_end);
-  if (rc2) return rc2;
-  memcpy(match12, h + o_m12, n1 * 4);
-  memcpy(nmatches, h + o_nm, sizeof(int));
-  return ORBX_OK;
+  CallArena A(device);
+  if (!A.ok()) return ORBX_ERR_HIP;
+  const BowSlots S(A, kf1, kf2, T, match12, nmatches);
+  rc = A.commit();
+  if (rc) return rc;
+  S.fill(A, kf1, kf2, T, nnratio, check_ori, sequential, th_low);
+  rc = A.upload();
+  if (rc) return rc;
+  const MatchShape sh = {1, (int)T.nps.size(), T.rows, sequential, T.max_n1, T.max_n2, kf2->n,
+                         upper_bytes_zero(kf1->desc, kf1->n) && upper_bytes_zero(kf2->desc, kf2->n)};
+  launch_match(A.d(S.prob), A.d(S.nps), sh, S.scratch(A), A.stream(), nullptr);
+  return A.finish();
 }
 
 extern "C" int orbm_search_by_bow(const orbx_bow_frame* kf1, const orbx_bow_frame* kf2,
@@ -330,12 +347,8 @@ extern "C" int orbm_search_by_bow_kf_frame(const orbx_bow_frame* kf, const orbx_
    * leave one row per KF index in the row -> candidate result while nmatches
    * counts both: rejected */
   if (kf && kf->n > 0 && kf->nnodes > 0 && kf->node_off && kf->feat) {
-    std::vector<unsigned char> seen((size_t)kf->n, 0);
-    for (uint32_t j = 0; j < kf->node_off[kf->nnodes]; ++j) {
-      const uint32_t i = kf->feat[j];
-      if (i >= (uint32_t)kf->n || seen[i]) return ORBX_ERR_ARG;
-      seen[i] = 1;
-    }
+    std::vector<uint8_t> seen((size_t)kf->n, 0);
+    if (index_repeats(seen, kf->feat, kf->node_off[kf->nnodes])) return ORBX_ERR_ARG;
   }
   orbx_bow_frame fr = *frame;
   fr.valid = nullptr;  /* every Frame feature is a candidate */
@@ -357,82 +370,23 @@ extern "C" int orbm_descriptor_distance_batch(const uint8_t* a, int na, const ui
   if (npairs == 0) return ORBX_OK;
   if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
-  WsLease L(device);
-  CallWs* w = L.w;
-  if (!w) return ORBX_ERR_HIP;
-  hipStream_t s = w->stream;
-  Carve C;
-  const size_t o_a = C.take((size_t)na * 32), o_b = C.take((size_t)nb * 32);
-  const size_t o_ia = C.take((size_t)npairs * 4), o_ib = C.take((size_t)npairs * 4);
-  const size_t in_end = C.off, o_d = C.take((size_t)npairs * 4), out_end = C.off;
-  int rc = w->reserve(out_end, out_end);
+  CallArena A(device);
+  if (!A.ok()) return ORBX_ERR_HIP;
+  const auto s_a = A.in(a, (size_t)na * 32), s_b = A.in(b, (size_t)nb * 32);
+  const auto s_ia = A.in(ia, (size_t)npairs), s_ib = A.in(ib, (size_t)npairs);
+  const auto s_d = A.out(dist, (size_t)npairs);
+  int rc = A.commit();
   if (rc) return rc;
-  uint8_t* h = w->h;
-  uint8_t* d = w->d;
-  memcpy(h + o_a, a, (size_t)na * 32);
-  memcpy(h + o_b, b, (size_t)nb * 32);
-  memcpy(h + o_ia, ia, (size_t)npairs * 4);
-  memcpy(h + o_ib, ib, (size_t)npairs * 4);
-  rc = stage_in(d, h, in_end, s);
+  rc = A.upload();
   if (rc) return rc;
-  hipLaunchKernelGGL(k_hamming_pairs, dim3((npairs + 255) / 256), dim3(256), 0, s, d + o_a, d + o_b,
-                     reinterpret_cast<const int32_t*>(d + o_ia),
-                     reinterpret_cast<const int32_t*>(d + o_ib), npairs,
-                     reinterpret_cast<int32_t*>(d + o_d));
-  rc = finish_call(w, o_d, out_end);
-  if (rc) return rc;
-  memcpy(dist, h + o_d, (size_t)npairs * 4);
-  return ORBX_OK;
+  hipLaunchKernelGGL(k_hamming_pairs, dim3((npairs + 255) / 256), dim3(256), 0, A.stream(), A.d(s_a),
+                     A.d(s_b), A.d(s_ia), A.d(s_ib), npairs, A.d(s_d));
+  return A.finish();
 }
 
 // ---------------------------------------------------------------------------
 // batched frame-pair matcher
 // ---------------------------------------------------------------------------
-namespace orbx {
-__global__ void k_match_setup(MProblem* probs, MNodePair* nps, int npairs,
-                              const orbx_keypoint* kps_a, const uint8_t* desc_a,
-                              const orbx_keypoint* kps_b, const uint8_t* desc_b, int kcap,
-                              int topn, const uint32_t* sel, int32_t* match12, int* nmatches,
-                              float nnratio, int check_ori, int* last_off) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npairs) return;
-  MProblem P;
-  P.desc1 = desc_a + (size_t)p * kcap * 32;
-  P.desc2 = desc_b + (size_t)p * kcap * 32;
-  P.ang1 = &kps_a[(size_t)p * kcap].angle;
-  P.ang2 = &kps_b[(size_t)p * kcap].angle;
-  P.valid1 = nullptr;
-  P.valid2 = nullptr;
-  P.feat1 = sel + ((size_t)p * 2 + 0) * topn;
-  P.feat2 = sel + ((size_t)p * 2 + 1) * topn;
-  P.match12 = match12 + (size_t)p * kcap;
-  P.nmatches = nmatches + p;
-  P.ang_stride = (int)(sizeof(orbx_keypoint) / sizeof(float));
-  P.n1 = 0;
-  P.n2 = 0;
-  P.np_begin = p;
-  P.np_end = p + 1;
-  P.row_begin = p * topn;
-  P.row_end = (p + 1) * topn;
-  P.check_ori = check_ori;
-  P.nnratio = nnratio;
-  P.sequential = 0;
-  P.dcap = orbm_dcap(nnratio);
-  P.th_low = ORBM_TH_LOW;
-  probs[p] = P;
-  MNodePair NP;
-  NP.prob = p;
-  NP.off1 = 0;
-  NP.n1 = 0;
-  NP.off2 = 0;
-  NP.n2 = 0;
-  NP.row_base = p * topn;
-  NP.g2 = p * topn;
-  nps[p] = NP;
-  last_off[p] = p * kcap;
-}
-}  // namespace orbx
-
 struct orbm_plan {
   int device = 0, max_pairs = 0, kcap = 0, topn = 0;
   /* ORBM_PLAN_ZERO_TAIL (opt-in, orbm_plan_set_options): the caller
@@ -445,20 +399,15 @@ struct orbm_plan {
   MProblem* d_probs = nullptr;
   MNodePair* d_nps = nullptr;
   uint32_t* d_sel = nullptr;
-  uint2* d_cand = nullptr;
-  uint4* d_gdesc2 = nullptr;
-  void* d_gx2 = nullptr; /* list2 as +-1 bytes, 256 B per position */
-  int4* d_rowinfo = nullptr;
-  int2* d_ev = nullptr;
-  int *d_last = nullptr, *d_last_off = nullptr;
+  MatchScratch sc; /* gval2 stays null: no validity masks */
   StageTimer timer;
 };
 
 static void mplan_free(orbm_plan* m) {
   if (!m) return;
   hipSetDevice(m->device);
-  void* b[] = {m->d_probs, m->d_nps, m->d_sel, m->d_cand, m->d_gdesc2, m->d_gx2, m->d_rowinfo,
-               m->d_ev, m->d_last, m->d_last_off};
+  void* b[] = {m->d_probs, m->d_nps, m->d_sel, m->sc.cand, m->sc.gdesc2, m->sc.gx2, m->sc.rowinfo,
+               m->sc.ev, m->sc.last, m->sc.last_off};
   for (void* p : b)
     if (p) hipFree(p);
   m->timer.release();
@@ -480,13 +429,13 @@ extern "C" int orbm_plan_create(int max_pairs, int kcap, int topn, int device, o
   if (hipMalloc((void**)&m->d_probs, P * sizeof(MProblem)) != hipSuccess ||
       hipMalloc((void**)&m->d_nps, P * sizeof(MNodePair)) != hipSuccess ||
       hipMalloc((void**)&m->d_sel, P * 2 * topn * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&m->d_cand, rows * ORBM_T * sizeof(uint2)) != hipSuccess ||
-      hipMalloc((void**)&m->d_gdesc2, rows * 2 * sizeof(uint4)) != hipSuccess ||
-      hipMalloc(&m->d_gx2, rows * 256) != hipSuccess ||
-      hipMalloc((void**)&m->d_rowinfo, rows * sizeof(int4)) != hipSuccess ||
-      hipMalloc((void**)&m->d_ev, rows * sizeof(int2)) != hipSuccess ||
-      hipMalloc((void**)&m->d_last, P * kcap * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&m->d_last_off, P * sizeof(int)) != hipSuccess) {
+      hipMalloc((void**)&m->sc.cand, rows * ORBM_T * sizeof(uint2)) != hipSuccess ||
+      hipMalloc((void**)&m->sc.gdesc2, rows * 2 * sizeof(uint4)) != hipSuccess ||
+      hipMalloc(&m->sc.gx2, rows * 256) != hipSuccess ||
+      hipMalloc((void**)&m->sc.rowinfo, rows * sizeof(int4)) != hipSuccess ||
+      hipMalloc((void**)&m->sc.ev, rows * sizeof(int2)) != hipSuccess ||
+      hipMalloc((void**)&m->sc.last, P * kcap * sizeof(int)) != hipSuccess ||
+      hipMalloc((void**)&m->sc.last_off, P * sizeof(int)) != hipSuccess) {
     mplan_free(m);
     return ORBX_ERR_HIP;
   }
@@ -532,12 +481,13 @@ extern "C" int orbm_plan_match_frames(orbm_plan* m, int npairs, const orbx_keypo
   m->timer.begin(ORBX_STAGE_MSELECT, s);
   hipLaunchKernelGGL(k_match_setup, dim3((npairs + 63) / 64), dim3(64), 0, s, m->d_probs,
                      m->d_nps, npairs, kps_a, desc_a, kps_b, desc_b, m->kcap, m->topn, m->d_sel,
-                     match12, nmatches, nnratio, check_ori ? 1 : 0, m->d_last_off);
+                     match12, nmatches, nnratio, check_ori ? 1 : 0, m->sc.last_off);
   hipLaunchKernelGGL(k_match_select, dim3(npairs, 2), dim3(256), 0, s, m->d_probs, m->d_nps,
                      kps_a, count_a, kps_b, count_b, m->kcap, m->topn, m->d_sel);
   m->timer.end(ORBX_STAGE_MSELECT, s);
-  launch_match(m->d_probs, npairs, m->d_nps, npairs, npairs * m->topn, 0, m->topn, m->topn,
-               m->kcap, m->d_gdesc2, nullptr, m->force_valu ? nullptr : m->d_gx2, m->d_cand, m->d_rowinfo, m->d_ev, m->d_last,
-               m->d_last_off, s, &m->timer, m->six_words);
+  const MatchShape sh = {npairs, npairs, npairs * m->topn, 0, m->topn, m->topn, m->kcap, m->six_words};
+  MatchScratch sc = m->sc;
+  if (m->force_valu) sc.gx2 = nullptr;
+  launch_match(m->d_probs, m->d_nps, sh, sc, s, &m->timer);
   return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
 }

@@ -6,7 +6,7 @@
 #include <algorithm>
 
 #include "../../include/orbx.h"
-#include "api_common.h"
+#include "call_arena.h"
 
 namespace orbx {
 struct UndistortArgs {
@@ -36,26 +36,17 @@ extern "C" int orbm_compute_distinctive_descriptors(const uint8_t* desc, const i
     if (off[m + 1] < off[m] || off[m + 1] - off[m] > (1 << 20)) return ORBX_ERR_ARG;
   int rc = select_device(device);
   if (rc) return rc;
-  WsLease L(device);
-  CallWs* w = L.w;
-  if (!w) return ORBX_ERR_HIP;
-  Carve C;
-  const size_t o_desc = C.take((size_t)total * 32), o_off = C.take((size_t)(nmp + 1) * 4);
-  const size_t in_end = C.off, o_best = C.take((size_t)nmp * 4);
-  rc = w->reserve(C.off, C.off);
+  CallArena A(device);
+  if (!A.ok()) return ORBX_ERR_HIP;
+  const auto s_desc = A.in(desc, (size_t)total * 32);
+  const auto s_off = A.in(off, (size_t)nmp + 1);
+  const auto s_best = A.out(best, (size_t)nmp);
+  rc = A.commit();
   if (rc) return rc;
-  if (total) memcpy(w->h + o_desc, desc, (size_t)total * 32);
-  memcpy(w->h + o_off, off, (size_t)(nmp + 1) * 4);
-  if (stage_in(w->d, w->h, in_end, w->stream)) return ORBX_ERR_HIP;
-  hipLaunchKernelGGL(k_distinctive, dim3((nmp + 3) / 4), dim3(256), 0, w->stream, w->d + o_desc,
-                     reinterpret_cast<const int32_t*>(w->d + o_off), nmp,
-                     reinterpret_cast<int32_t*>(w->d + o_best));
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  ORBX_TRY(hipMemcpyAsync(w->h + o_best, w->d + o_best, (size_t)nmp * 4, hipMemcpyDeviceToHost,
-                          w->stream));
-  ORBX_TRY(stream_wait(w->stream));
-  memcpy(best, w->h + o_best, (size_t)nmp * 4);
-  return ORBX_OK;
+  if (A.upload()) return ORBX_ERR_HIP;
+  hipLaunchKernelGGL(k_distinctive, dim3((nmp + 3) / 4), dim3(256), 0, A.stream(), A.d(s_desc),
+                     A.d(s_off), nmp, A.d(s_best));
+  return A.finish();
 }
 
 extern "C" int orbx_undistort_keypoints(const orbx_keypoint* kps, int n, const float* K,
@@ -79,26 +70,16 @@ extern "C" int orbx_undistort_keypoints(const orbx_keypoint* kps, int n, const f
   A.ifx = 1. / A.fx;
   A.ify = 1. / A.fy;
   for (int j = 0; j < ndist; ++j) A.k[j] = dist[j];
-  WsLease L(device);
-  CallWs* w = L.w;
-  if (!w) return ORBX_ERR_HIP;
-  Carve C;
-  const size_t o_in = C.take((size_t)n * sizeof(orbx_keypoint));
-  const size_t o_out = C.take((size_t)n * sizeof(orbx_keypoint));
-  rc = w->reserve(C.off, C.off);
+  CallArena ar(device);
+  if (!ar.ok()) return ORBX_ERR_HIP;
+  const auto s_in = ar.in(kps, (size_t)n);
+  const auto s_out = ar.out(out, (size_t)n);
+  rc = ar.commit();
   if (rc) return rc;
-  memcpy(w->h + o_in, kps, (size_t)n * sizeof(orbx_keypoint));
-  if (stage_in(w->d + o_in, w->h + o_in, ((size_t)n * sizeof(orbx_keypoint) + 15) & ~(size_t)15, w->stream))
-    return ORBX_ERR_HIP;
-  hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, w->stream,
-                     reinterpret_cast<const orbx_keypoint*>(w->d + o_in), n, A,
-                     reinterpret_cast<orbx_keypoint*>(w->d + o_out));
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  ORBX_TRY(hipMemcpyAsync(w->h + o_out, w->d + o_out, (size_t)n * sizeof(orbx_keypoint),
-                          hipMemcpyDeviceToHost, w->stream));
-  ORBX_TRY(stream_wait(w->stream));
-  memcpy(out, w->h + o_out, (size_t)n * sizeof(orbx_keypoint));
-  return ORBX_OK;
+  if (ar.upload()) return ORBX_ERR_HIP;
+  hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, ar.stream(), ar.d(s_in), n, A,
+                     ar.d(s_out));
+  return ar.finish();
 }
 
 extern "C" size_t orbx_boundary_record_bytes(int kcap) {

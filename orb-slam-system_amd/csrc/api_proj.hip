@@ -2,13 +2,10 @@
 // (query form, /root/reference/src/ORBmatcher.cc:19-61,732-818,820-894).
 #include <hip/hip_runtime.h>
 
-#include <string.h>
-
 #include <algorithm>
-#include <vector>
 
 #include "../../include/orbx.h"
-#include "api_common.h"
+#include "call_arena.h"
 
 namespace orbx {
 struct ProjFrame {
@@ -81,53 +78,42 @@ extern "C" int orbm_search_by_projection(int mode, const orbx_proj_frame* F,
   if (n == 0 || nq == 0) return ORBX_OK;
   if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
-  WsLease L(device);
-  CallWs* w = L.w;
-  if (!w) return ORBX_ERR_HIP;
-  hipStream_t s = w->stream;
+  CallArena A(device);
+  if (!A.ok()) return ORBX_ERR_HIP;
   set_max_dynamic_lds((const void*)k_grid_build, device);
   set_max_dynamic_lds((const void*)k_proj_resolve, device);
-  Carve C;
-  const size_t o_keys = C.take((size_t)n * sizeof(orbx_keypoint)), o_desc = C.take((size_t)n * 32);
-  const size_t o_ur = F->uright ? C.take((size_t)n * 4) : 0, o_occ = F->occupied ? C.take(n) : 0;
-  const size_t o_q = C.take((size_t)nq * sizeof(orbx_query_proj)), o_qd = C.take((size_t)nq * 32);
-  const size_t o_prob = C.take(sizeof(ProjProblem));
-  const size_t in_end = C.off;
-  const size_t o_match = C.take((size_t)n * 4), o_nm = C.take(4), out_end = C.off;
-  const size_t o_off = C.take((PG_CELLS + 1) * 4), o_feat = C.take((size_t)n * 4);
-  const size_t o_cand = C.take((size_t)nq * PJ_T * 4), o_nc = C.take((size_t)nq * 4);
-  int rc = w->reserve(C.off, out_end);
+  const auto s_keys = A.in(F->keys, (size_t)n);
+  const auto s_desc = A.in(F->desc, (size_t)n * 32);
+  const auto s_ur = A.in_opt(F->uright, (size_t)n);
+  const auto s_occ = A.in_opt(F->occupied, (size_t)n);
+  const auto s_q = A.in(q, (size_t)nq);
+  const auto s_qd = A.in(qdesc, (size_t)nq * 32);
+  const auto s_prob = A.in<ProjProblem>(1);
+  const auto s_match = A.out(match, (size_t)n);
+  const auto s_nm = A.out(nmatches, 1);
+  const auto s_off = A.scratch<int>(PG_CELLS + 1), s_feat = A.scratch<int>((size_t)n);
+  const auto s_cand = A.scratch<uint32_t>((size_t)nq * PJ_T);
+  const auto s_nc = A.scratch<int>((size_t)nq);
+  const int rc = A.commit();
   if (rc) return rc;
-  uint8_t* h = w->h;
-  uint8_t* d = w->d;
-  memcpy(h + o_keys, F->keys, (size_t)n * sizeof(orbx_keypoint));
-  memcpy(h + o_desc, F->desc, (size_t)n * 32);
-  if (F->uright) memcpy(h + o_ur, F->uright, (size_t)n * 4);
-  if (F->occupied) memcpy(h + o_occ, F->occupied, n);
-  memcpy(h + o_q, q, (size_t)nq * sizeof(orbx_query_proj));
-  memcpy(h + o_qd, qdesc, (size_t)nq * 32);
-  ProjProblem* hp = reinterpret_cast<ProjProblem*>(h + o_prob);
-  ProjProblem* dp = reinterpret_cast<ProjProblem*>(d + o_prob);
+  ProjProblem* hp = A.h(s_prob);
   hp->F = proj_frame(F);
-  hp->keys = reinterpret_cast<orbx_keypoint*>(d + o_keys);
-  hp->desc = d + o_desc;
-  hp->uright = F->uright ? reinterpret_cast<float*>(d + o_ur) : nullptr;
-  hp->occupied = F->occupied ? d + o_occ : nullptr;
-  hp->qs = reinterpret_cast<orbx_query_proj*>(d + o_q);
-  hp->qdesc = d + o_qd;
+  hp->keys = A.d(s_keys);
+  hp->desc = A.d(s_desc);
+  hp->uright = A.d(s_ur);
+  hp->occupied = A.d(s_occ);
+  hp->qs = A.d(s_q);
+  hp->qdesc = A.d(s_qd);
   hp->nq = nq;
-  hp->match = reinterpret_cast<int32_t*>(d + o_match);
-  hp->nmatches = reinterpret_cast<int*>(d + o_nm);
-  hp->cell_off = reinterpret_cast<int*>(d + o_off);
-  hp->cell_feat = reinterpret_cast<int*>(d + o_feat);
-  hp->cand = reinterpret_cast<uint32_t*>(d + o_cand);
-  hp->ncand = reinterpret_cast<int*>(d + o_nc);
-  if (stage_in(d, h, in_end, s)) return ORBX_ERR_HIP;
-  launch_proj(dp, 1, n, nq, mode, nnratio, th_dist, check_ori, s);
-  if (finish_call(w, in_end, out_end)) return ORBX_ERR_HIP;
-  memcpy(match, h + o_match, (size_t)n * 4);
-  memcpy(nmatches, h + o_nm, sizeof(int));
-  return ORBX_OK;
+  hp->match = A.d(s_match);
+  hp->nmatches = A.d(s_nm);
+  hp->cell_off = A.d(s_off);
+  hp->cell_feat = A.d(s_feat);
+  hp->cand = A.d(s_cand);
+  hp->ncand = A.d(s_nc);
+  if (A.upload()) return ORBX_ERR_HIP;
+  launch_proj(A.d(s_prob), 1, n, nq, mode, nnratio, th_dist, check_ori, A.stream());
+  return A.finish();
 }
 
 // ---------------------------------------------------------------------------

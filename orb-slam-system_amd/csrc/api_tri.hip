@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "../../include/orbx.h"
-#include "api_common.h"
+#include "call_arena.h"
 #include "tri_internal.h"
 
 namespace orbx {
@@ -34,40 +34,31 @@ int check_tri_frame(const orbx_tri_frame* k, bool kf2) {
   return ORBX_OK;
 }
 
-// offsets of one frame's inputs in the arena
-struct FrameOff {
-  size_t key, desc, mp, feat, sigma2;
-  uint32_t nf;
-};
+// one frame's inputs in the arena: declared by the constructor (kf2: with the
+// level_sigma2 table), the keys converted in place and the device view taken
+// once the arena is committed
+struct FrameSlots {
+  Slot<TriKey> key;
+  Slot<uint8_t> desc, mp;
+  Slot<uint32_t> feat;
+  Slot<float> sigma2;
 
-FrameOff carve_frame(Carve& C, const orbx_tri_frame* k, bool kf2) {
-  FrameOff o;
-  o.nf = k->nnodes ? k->node_off[k->nnodes] : 0;
-  o.key = C.take((size_t)k->n * sizeof(TriKey));
-  o.desc = C.take((size_t)k->n * 32);
-  o.mp = k->has_mp ? C.take((size_t)k->n) : 0;
-  o.feat = C.take((size_t)o.nf * 4);
-  o.sigma2 = kf2 ? C.take((size_t)k->nlevels * 4) : 0;
-  return o;
-}
-
-TriFrame fill_frame(uint8_t* h, uint8_t* d, const FrameOff& o, const orbx_tri_frame* k, bool kf2) {
-  TriKey* hk = reinterpret_cast<TriKey*>(h + o.key);
-  for (int i = 0; i < k->n; ++i) {
-    const orbx_keypoint& p = k->keys[i];
-    hk[i] = TriKey{p.x, p.y, p.angle, p.octave};
+  FrameSlots(CallArena& A, const orbx_tri_frame* k, bool kf2) {
+    key = A.in<TriKey>((size_t)k->n);
+    desc = A.in(k->desc, (size_t)k->n * 32);
+    mp = A.in_opt(k->has_mp, (size_t)k->n);
+    feat = A.in(k->feat, k->nnodes ? k->node_off[k->nnodes] : 0);
+    if (kf2) sigma2 = A.in(k->level_sigma2, (size_t)k->nlevels);
   }
-  if (k->n) memcpy(h + o.desc, k->desc, (size_t)k->n * 32);
-  if (k->has_mp && k->n) memcpy(h + o.mp, k->has_mp, (size_t)k->n);
-  if (o.nf) memcpy(h + o.feat, k->feat, (size_t)o.nf * 4);
-  if (kf2 && k->nlevels) memcpy(h + o.sigma2, k->level_sigma2, (size_t)k->nlevels * 4);
-  TriFrame f;
-  f.key = reinterpret_cast<const TriKey*>(d + o.key);
-  f.desc = d + o.desc;
-  f.has_mp = k->has_mp ? d + o.mp : nullptr;
-  f.feat = reinterpret_cast<const uint32_t*>(d + o.feat);
-  return f;
-}
+  TriFrame fill(const CallArena& A, const orbx_tri_frame* k) const {
+    TriKey* hk = A.h(key);
+    for (int i = 0; i < k->n; ++i) {
+      const orbx_keypoint& p = k->keys[i];
+      hk[i] = TriKey{p.x, p.y, p.angle, p.octave};
+    }
+    return TriFrame{A.d(key), A.d(desc), A.d(mp), A.d(feat)};
+  }
+};
 
 }  // namespace
 
@@ -87,11 +78,8 @@ extern "C" int orbm_search_for_triangulation(const orbx_tri_frame* kf1, int nkf2
   {
     /* a KF1 feature listed twice (never in a DBoW2 FeatureVector) would be one
      * match12 entry searched and counted twice (ORBmatcher.cc:431-432) */
-    std::vector<unsigned char> seen(kf1->n > 0 ? (size_t)kf1->n : 1, 0);
-    for (uint32_t j = 0; j < nf1; ++j) {
-      if (seen[kf1->feat[j]]) return ORBX_ERR_ARG;
-      seen[kf1->feat[j]] = 1;
-    }
+    std::vector<uint8_t> seen((size_t)kf1->n, 0);
+    if (index_repeats(seen, kf1->feat, nf1)) return ORBX_ERR_ARG;
   }
   if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   const size_t n1 = (size_t)kf1->n;
@@ -102,88 +90,58 @@ extern "C" int orbm_search_for_triangulation(const orbx_tri_frame* kf1, int nkf2
     for (int p = 0; p < nkf2; ++p) nmatches[p] = 0;
     return ORBX_OK;
   }
-  // the common nodes of every problem, ascending (:396-442: the iterator that
-  // is behind jumps with lower_bound), cut into items of TRI_ROWS rows
+  // the common nodes of every problem, ascending (:396-442), cut into items
+  // of TRI_ROWS rows
   std::vector<TriItem> items;
   for (int p = 0; p < nkf2; ++p) {
-    const orbx_tri_frame* k2 = kf2 + p;
-    const uint32_t *b1 = kf1->node_id, *e1 = b1 + kf1->nnodes;
-    const uint32_t *b2 = k2->node_id, *e2 = b2 + k2->nnodes;
-    const uint32_t *f1 = b1, *f2 = b2;
-    while (f1 != e1 && f2 != e2) {
-      if (*f1 == *f2) {
-        const uint32_t o1 = kf1->node_off[f1 - b1], c1 = kf1->node_off[f1 - b1 + 1] - o1;
-        const uint32_t o2 = k2->node_off[f2 - b2], c2 = k2->node_off[f2 - b2 + 1] - o2;
-        if (o1 > 0x7FFFFFFFu - c1 || o2 > 0x7FFFFFFFu - c2) return ORBX_ERR_UNSUPPORTED;
-        for (uint32_t r = 0; r < c1 && c2 > 0; r += TRI_ROWS) {
-          TriItem it;
-          it.prob = p;
-          it.off1 = (int)(o1 + r);
-          it.n1 = (int)std::min<uint32_t>(TRI_ROWS, c1 - r);
-          it.off2 = (int)o2;
-          it.n2 = (int)c2;
-          items.push_back(it);
-        }
-        ++f1;
-        ++f2;
-      } else if (*f1 < *f2) {
-        f1 = std::lower_bound(f1, e1, *f2);
-      } else {
-        f2 = std::lower_bound(f2, e2, *f1);
-      }
-    }
+    const auto cut = [&](uint32_t o1, uint32_t c1, uint32_t o2, uint32_t c2) {
+      if (o1 > 0x7FFFFFFFu - c1 || o2 > 0x7FFFFFFFu - c2) return ORBX_ERR_UNSUPPORTED;
+      for (uint32_t r = 0; r < c1 && c2 > 0; r += TRI_ROWS)
+        items.push_back(
+            TriItem{p, (int)(o1 + r), (int)std::min<uint32_t>(TRI_ROWS, c1 - r), (int)o2, (int)c2});
+      return ORBX_OK;
+    };
+    rc = for_common_nodes(kf1->node_id, kf1->node_off, kf1->nnodes, kf2[p].node_id, kf2[p].node_off,
+                          kf2[p].nnodes, cut);
+    if (rc) return rc;
   }
   if (items.size() > 0x7FFFFFFFu || nkf2 > 65535) return ORBX_ERR_UNSUPPORTED; /* grid limits */
   ORBX_TRY(hipSetDevice(device));
-  WsLease L(device);
-  CallWs* w = L.w;
-  if (!w) return ORBX_ERR_HIP;
-  hipStream_t s = w->stream;
-  // one arena: inputs [0, in_end) go up in one copy from pinned staging,
-  // outputs [in_end, out_end) come back in one copy, scratch after them
-  Carve C;
-  const FrameOff o1 = carve_frame(C, kf1, false);
-  std::vector<FrameOff> o2((size_t)nkf2);
-  for (int p = 0; p < nkf2; ++p) o2[p] = carve_frame(C, kf2 + p, true);
-  const size_t o_prob = C.take((size_t)nkf2 * sizeof(TriProblem));
-  const size_t o_items = C.take(items.size() * sizeof(TriItem));
-  const size_t in_end = C.off;
-  const size_t o_m12 = C.take((size_t)nkf2 * n1 * 4), o_nm = C.take((size_t)nkf2 * sizeof(int));
-  const size_t out_end = C.off;
-  const size_t o_row = C.take((size_t)nkf2 * n1 * sizeof(int2));
-  const size_t o_hist = C.take((size_t)nkf2 * 32 * sizeof(int));
-  rc = w->reserve(C.off, out_end);
+  CallArena A(device);
+  if (!A.ok()) return ORBX_ERR_HIP;
+  const FrameSlots s1(A, kf1, false);
+  std::vector<FrameSlots> s2;
+  for (int p = 0; p < nkf2; ++p) s2.emplace_back(A, kf2 + p, true);
+  const auto s_prob = A.in<TriProblem>((size_t)nkf2);
+  const auto s_items = A.in(items.data(), items.size());
+  const auto s_m12 = A.out(match12, (size_t)nkf2 * n1);
+  const auto s_nm = A.out(nmatches, (size_t)nkf2);
+  const auto s_row = A.scratch<int2>((size_t)nkf2 * n1);
+  const auto s_hist = A.scratch<int>((size_t)nkf2 * 32);
+  rc = A.commit();
   if (rc) return rc;
-  uint8_t* d = w->d;
-  uint8_t* h = w->h;
-  const TriFrame f1 = fill_frame(h, d, o1, kf1, false);
-  TriProblem* hp = reinterpret_cast<TriProblem*>(h + o_prob);
+  const TriFrame f1 = s1.fill(A, kf1);
   for (int p = 0; p < nkf2; ++p) {
-    TriProblem P;
-    memset(&P, 0, sizeof(P));
-    P.kf2 = fill_frame(h, d, o2[p], kf2 + p, true);
-    P.sigma2 = reinterpret_cast<const float*>(d + o2[p].sigma2);
+    TriProblem P = {};
+    P.kf2 = s2[p].fill(A, kf2 + p);
+    P.sigma2 = A.d(s2[p].sigma2);
     memcpy(P.F, F12 + (size_t)p * 9, sizeof(P.F));
-    P.row = reinterpret_cast<int2*>(d + o_row) + (size_t)p * n1;
-    P.hist = reinterpret_cast<int*>(d + o_hist) + (size_t)p * 32;
-    P.match12 = reinterpret_cast<int32_t*>(d + o_m12) + (size_t)p * n1;
-    P.nmatches = reinterpret_cast<int*>(d + o_nm) + p;
-    memcpy(hp + p, &P, sizeof(P));
+    P.row = A.d(s_row) + (size_t)p * n1;
+    P.hist = A.d(s_hist) + (size_t)p * 32;
+    P.match12 = A.d(s_m12) + (size_t)p * n1;
+    P.nmatches = A.d(s_nm) + p;
+    A.h(s_prob)[p] = P;
   }
-  if (!items.empty()) memcpy(h + o_items, items.data(), items.size() * sizeof(TriItem));
-  rc = stage_in(d, h, in_end, s);
+  rc = A.upload();
   if (rc) return rc;
-  const TriProblem* d_probs = reinterpret_cast<const TriProblem*>(d + o_prob);
+  const TriProblem* d_probs = A.d(s_prob);
+  hipStream_t s = A.stream();
   hipLaunchKernelGGL(k_tri_init, dim3((unsigned)((n1 + 255) / 256), nkf2), dim3(256), 0, s, d_probs,
                      (int)n1);
   if (!items.empty())
     hipLaunchKernelGGL(k_tri_search, dim3((unsigned)items.size()), dim3(TRI_ROWS), 0, s, d_probs,
-                       reinterpret_cast<const TriItem*>(d + o_items), f1, check_ori ? 1 : 0);
+                       A.d(s_items), f1, check_ori ? 1 : 0);
   hipLaunchKernelGGL(k_tri_finalize, dim3(nkf2), dim3(256), 0, s, d_probs, (int)n1,
                      check_ori ? 1 : 0);
-  rc = finish_call(w, in_end, out_end);
-  if (rc) return rc;
-  memcpy(match12, h + o_m12, (size_t)nkf2 * n1 * 4);
-  memcpy(nmatches, h + o_nm, (size_t)nkf2 * sizeof(int));
-  return ORBX_OK;
+  return A.finish();
 }

@@ -8,8 +8,9 @@
 // pairs of a well-formed FeatureVector touch disjoint KF2 features and run
 // in parallel), then finalize.  Launched by launch_match (api_match.hip)
 // unless another launcher is named:
-//   k_match_select        batched plan only (orbm_plan_match_frames), before
-//                         launch_match: top-n keypoints of each frame
+//   k_match_setup         batched plan only (orbm_plan_match_frames), before
+//   k_match_select        launch_match: the problem and node-pair tables,
+//                         then the top-n keypoints of each frame
 //   k_match_expand2       candidates on the matrix cores (at most 65535 node
 //   k_match_cand_mfma     pairs, no validity arrays, ORBM_MFMA): list2 as
 //                         +-1 operands, then distances by MFMA
@@ -1438,6 +1439,51 @@ __global__ __launch_bounds__(256) void k_match_finalize(const MProblem* __restri
   atomicAdd(&s_nfilt, nf);
   __syncthreads();
   if (tid == 0) *P.nmatches = s_nev - s_nfilt;
+}
+
+// the batched frame-pair matcher's tables (orbm_plan_match_frames): problem p
+// is frame pair p, one node pair over its two top-N selections
+__global__ void k_match_setup(MProblem* probs, MNodePair* nps, int npairs,
+                              const orbx_keypoint* kps_a, const uint8_t* desc_a,
+                              const orbx_keypoint* kps_b, const uint8_t* desc_b, int kcap,
+                              int topn, const uint32_t* sel, int32_t* match12, int* nmatches,
+                              float nnratio, int check_ori, int* last_off) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npairs) return;
+  MProblem P;
+  P.desc1 = desc_a + (size_t)p * kcap * 32;
+  P.desc2 = desc_b + (size_t)p * kcap * 32;
+  P.ang1 = &kps_a[(size_t)p * kcap].angle;
+  P.ang2 = &kps_b[(size_t)p * kcap].angle;
+  P.valid1 = nullptr;
+  P.valid2 = nullptr;
+  P.feat1 = sel + ((size_t)p * 2 + 0) * topn;
+  P.feat2 = sel + ((size_t)p * 2 + 1) * topn;
+  P.match12 = match12 + (size_t)p * kcap;
+  P.nmatches = nmatches + p;
+  P.ang_stride = (int)(sizeof(orbx_keypoint) / sizeof(float));
+  P.n1 = 0;
+  P.n2 = 0;
+  P.np_begin = p;
+  P.np_end = p + 1;
+  P.row_begin = p * topn;
+  P.row_end = (p + 1) * topn;
+  P.check_ori = check_ori;
+  P.nnratio = nnratio;
+  P.sequential = 0;
+  P.dcap = orbm_dcap(nnratio);
+  P.th_low = ORBM_TH_LOW;
+  probs[p] = P;
+  MNodePair NP;
+  NP.prob = p;
+  NP.off1 = 0;
+  NP.n1 = 0;
+  NP.off2 = 0;
+  NP.n2 = 0;
+  NP.row_base = p * topn;
+  NP.g2 = p * topn;
+  nps[p] = NP;
+  last_off[p] = p * kcap;
 }
 
 // ---------------------------------------------------------------------------

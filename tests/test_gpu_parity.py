@@ -689,3 +689,131 @@ def test_search_by_bow_many_node_pairs(gpu, oracle, many_nodes_bow, masked):
     m, nm = gpu.search_by_bow(kf1, kf2, 0.75, True)
     assert nm == rnm
     assert np.array_equal(m, rm)
+
+
+@pytest.fixture(scope="module")
+def dropin_calls(oracle):
+    """name -> check(gpu): one small call of every synchronous drop-in entry
+    point (all seven share the pooled per-call workspace), each compared with
+    the reference its own test module uses, plus one large SearchByBoW.  The
+    inputs and references are made once and left unchanged."""
+    import kfwindow_util as KW
+    import triangulation_util as TR
+    from test_projection import _frame, _queries
+    from test_rank4 import EUROC_D, EUROC_K, _kps
+
+    rng = np.random.default_rng(2024)
+    calls = {}
+
+    def bow(kf1, kf2):
+        rm, rnm = oracle.search_by_bow(kf1, kf2, 0.75, True)
+        assert rnm > 0
+
+        def check(gpu):
+            m, nm = gpu.search_by_bow(kf1, kf2, 0.75, True)
+            assert nm == rnm and np.array_equal(m, rm)
+        return check
+
+    d1 = rng.integers(0, 256, (130, 32), dtype=np.uint8)
+    d2 = _correlated(rng, d1[rng.integers(0, 130, 130)], rng.integers(0, 40, 130))
+    kf1, kf2 = _random_bow(rng, 130, 3, 3, d1), _random_bow(rng, 130, 3, 3, d2)
+    calls["bow_masked"] = bow(kf1, kf2)
+    calls["bow_unmasked"] = bow(dict(kf1, valid=None), dict(kf2, valid=None))
+    n = 2000
+    b1 = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    b2 = _correlated(rng, b1[rng.permutation(n)], rng.integers(0, 40, n))
+    one = lambda d: dict(desc=d, angle=rng.uniform(0, 360, n).astype(np.float32), valid=None,
+                         node_id=np.array([7], np.uint32), off=np.array([0, n], np.uint32),
+                         feat=np.arange(n, dtype=np.uint32))
+    calls["bow_large"] = bow(one(b1), one(b2))
+
+    ia, ib = rng.integers(0, 130, 5).astype(np.int32), rng.integers(0, 130, 5).astype(np.int32)
+    want_dist = np.array([oracle.descriptor_distance(d1[i], d2[j]) for i, j in zip(ia, ib)])
+
+    def dist(gpu):
+        assert np.array_equal(gpu.descriptor_distance_batch(d1, d2, ia, ib), want_dist)
+    calls["distance"] = dist
+
+    def proj(uright):
+        fr = _frame(oracle, 2, uright=uright, seed=5)
+        fr = dict(fr, keys=fr["keys"][:200].copy(), desc=fr["desc"][:200].copy())
+        if uright:
+            fr["uright"] = fr["uright"][:200].copy()
+        q, qd = _queries(oracle, fr, 50, 9, 2, dup=0.3)
+        rm, rn = oracle.search_by_projection(2, fr, q, qd, 0.75, 100, True)
+        assert rn > 0
+
+        def check(gpu):
+            gm, gn = gpu.search_by_projection(2, fr, q, qd, 0.75, 100, True)
+            assert gn == rn and np.array_equal(gm, rm)
+        return check
+    calls["proj_uright"] = proj(True)
+    calls["proj_mono"] = proj(False)
+
+    t1, t2s, Fs = TR.make_case(31, {2: 40, 4: 70, 6: 30}, [{2: 50, 4: 60, 6: 40}, {2: 30, 4: 50, 6: 70}])
+    assert [len(k["keys"]) for k in t2s] == [150, 150]
+    tm, tnm, _ = TR.ref_batch(t1, t2s, Fs)
+    assert tnm.sum() > 0
+
+    def tri(gpu):
+        gm, gn = gpu.search_for_triangulation(t1, t2s, Fs)
+        assert np.array_equal(gm, tm) and np.array_equal(gn, tnm)
+    calls["triangulation"] = tri
+
+    krng = np.random.RandomState(23)
+    kfs = [KW.make_frame(krng, 100) for _ in range(3)]
+    qa, pa = KW.make_queries(krng, kfs[0], 40)
+    qc, pc = KW.make_queries(krng, kfs[2], 25)
+    qc["desc"] += len(pa)
+    pool = np.concatenate([pa, pc])
+    qs = [qa, qa[:0], qc]  # the middle keyframe has no queries
+    kwant = [KW.ref_search(kfs[0], qa, pool), None, KW.ref_search(kfs[2], qc, pool)]
+    assert all((w[0] >= 0).any() for w in kwant if w)
+
+    def kfwin(gpu):
+        got = gpu.keyframe_search(kfs, qs, pool)
+        assert len(got[1][0]) == 0 and len(got[1][1]) == 0
+        for p in (0, 2):
+            assert np.array_equal(got[p][0], kwant[p][0]) and np.array_equal(got[p][1], kwant[p][1])
+    calls["keyframe_search"] = kfwin
+
+    groups = [_correlated(rng, np.repeat(rng.integers(0, 256, (1, 32), dtype=np.uint8), g, 0),
+                          rng.integers(0, 30, g)) for g in (5, 1, 8)]
+    want_best = np.array([oracle.distinctive_descriptor(g) for g in groups], np.int32)
+
+    def distinctive(gpu):
+        assert np.array_equal(gpu.compute_distinctive_descriptors(groups), want_best)
+    calls["distinctive"] = distinctive
+
+    kp = _kps(oracle, 752, 480, 6)[:17].copy()
+    want_un = oracle.undistort_keypoints(kp, EUROC_K, EUROC_D)
+    assert len(kp) == 17 and not np.array_equal(want_un["x"], kp["x"])
+
+    def undistort(gpu):
+        got = gpu.undistort_keypoints(kp, EUROC_K, EUROC_D)
+        assert np.array_equal(got.view(np.uint8), want_un.view(np.uint8))
+    calls["undistort"] = undistort
+    return calls
+
+
+DROPIN_ORDERS = [
+    ["bow_masked", "distance", "proj_uright", "triangulation", "keyframe_search", "bow_large",
+     "distinctive", "undistort", "bow_unmasked", "proj_mono"],
+    ["undistort", "keyframe_search", "proj_mono", "bow_unmasked", "distinctive", "bow_large",
+     "triangulation", "distance", "proj_uright", "bow_masked"],
+]
+
+
+def test_dropin_calls_interleaved_on_the_pooled_workspace(gpu, dropin_calls):
+    """Every synchronous drop-in entry point leases the same pooled workspace
+    (csrc/call_arena.h): no call may leave work, sizes or contents behind
+    that the next one sees.  All seven are interleaved in two fixed orders,
+    each order twice, at the smallest shapes with every slot kind (optional
+    inputs present and absent, in-place tables, a keyframe without queries);
+    a 2000 x 2000 SearchByBoW in the middle of each pass grows the arena, so
+    the small calls after it run inside a larger one."""
+    assert all(sorted(o) == sorted(dropin_calls) for o in DROPIN_ORDERS)
+    for order in DROPIN_ORDERS:
+        for _ in range(2):
+            for name in order:
+                dropin_calls[name](gpu)

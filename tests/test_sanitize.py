@@ -3,7 +3,8 @@ build): `make sanitize` compiles geometry.cpp and every API translation unit
 with -fsanitize=address,undefined on the host side only (-Xarch_host; no GPU
 sanitizer), links tests/cpp/sanitize_main.cpp, and runs it on the CPU:
 geometry planning over a size/parameter sweep plus malformed-argument calls
-of every entry point.  Leak checking is off (the HIP runtime keeps its
+of every entry point; and tests/cpp/arena_main.cpp, the drop-in calls' typed
+arena (csrc/call_arena.h) over two host buffers.  Leak checking is off (the HIP runtime keeps its
 allocations until exit)."""
 import os
 import subprocess
@@ -20,3 +21,8 @@ def test_host_code_clean_under_asan_ubsan():
     assert r.returncode == 0, r.stdout + r.stderr
     assert "0 failures" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    a = subprocess.run([os.path.join(PKG, "build_asan", "arena_main")], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert a.returncode == 0, a.stdout + a.stderr
+    assert "0 failures" in a.stdout
+    assert "runtime error" not in a.stderr and "AddressSanitizer" not in a.stderr
