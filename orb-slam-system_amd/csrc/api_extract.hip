@@ -390,7 +390,7 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
       upload(&p->d_xofs1, P.xofs1, us) || upload(&p->d_yofs, P.yofs, us) ||
       upload(&p->d_alpha, P.alpha, us) || upload(&p->d_beta, P.beta, us) ||
       upload(&p->d_pyr_xs, P.pyr_xs, us) || upload(&p->d_pyr_ys, P.pyr_ys, us) ||
-      upload(&p->d_pyr_bo, P.pyr_bo, us) || upload(&p->d_pyr_blob, P.pyr_blob, us)) {
+      upload(&p->d_pyr_bo, P.pyr_bo, us) || upload(&p->d_pyr_blob, P.pyr_kblob, us)) {
     plan_free(p);
     return ORBX_ERR_HIP;
   }

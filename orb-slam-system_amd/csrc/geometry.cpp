@@ -273,10 +273,18 @@ static bool try_segment(Plan& P, const std::vector<int>& lev, int TW, int TH, Py
   return true;
 }
 
-/* per tile column / row LUT blobs (layout: orbx_internal.h) */
+/* per tile column / row LUT blobs (layout: orbx_internal.h), in two forms of
+ * the same entries at the same offsets: P.pyr_blob holds plain source offsets
+ * and coefficients (tests/cpp/pyramid_emu.cpp replays the tiling from it),
+ * P.pyr_kblob is what k_pyramid reads.  They differ in the column entries
+ * only: the kernel's v_perm selectors place the source byte in the high byte
+ * of each u16 half (0x0C = zero below it) and its coefficient pair is
+ * 16*a0 | 16*a1 << 16, so that the dot product is 4096*D (pyr_arith.h). */
 /* returns false when k_pyramid's packed arithmetic does not apply: the 4
  * columns of a thread must read bytes within 8 of the first one's sx, and
- * every coefficient must lie in [0, 4095] (INTER_LINEAR downscale: [0, 2048]) */
+ * every coefficient pair must lie in [0, 2048] and sum to 2048 (INTER_LINEAR's
+ * scale: the kernel's bound 4096*D <= 255*2048*4096 < 2^32 and its carry-free
+ * packed rounding depend on it) */
 static bool build_blobs(Plan& P, const std::vector<int>& lev, PyrSeg& g, const std::vector<Iv>& xs,
                         const std::vector<Iv>& ys) {
   const int ns = (int)lev.size();
@@ -309,7 +317,7 @@ static bool build_blobs(Plan& P, const std::vector<int>& lev, PyrSeg& g, const s
           int lo, hi;
           src_span(P, lev[s], isx, dd, lo, hi);
           const int16_t* cf = isx ? &P.alpha[2 * (lv.lut_x + dd)] : &P.beta[2 * (lv.lut_y + dd)];
-          if (cf[0] < 0 || cf[0] > 4095 || cf[1] < 0 || cf[1] > 4095) return false;
+          if (cf[0] < 0 || cf[0] > 2048 || cf[1] < 0 || cf[1] > 2048 || cf[0] + cf[1] != 2048) return false;
           if (isx && ((d - b) & 3) == 0) glo = lo;
           if (isx && hi - glo > 7) return false;
           if (!isx) { /* LDS byte offsets of the two source rows (< 64 KiB) */
@@ -318,16 +326,27 @@ static bool build_blobs(Plan& P, const std::vector<int>& lev, PyrSeg& g, const s
             const uint32_t o1 = base + (uint32_t)(hi - origin) * (uint32_t)g.lpitch[s - 1];
             if (o0 > 0xFFFF || o1 > 0xFFFF) return false;
             P.pyr_blob.push_back(o0 | (o1 << 16));
+            P.pyr_kblob.push_back(o0 | (o1 << 16));
           }
-          else if (((d - b) & 3) == 0) /* group column 0: s0 | (sx1 - s0) << 16 */
+          else if (((d - b) & 3) == 0) { /* group column 0: s0 | (sx1 - s0) << 16 (the kernel builds its selector) */
             P.pyr_blob.push_back((uint32_t)(lo - origin) | ((uint32_t)(hi - lo) << 16));
-          else /* columns 1..3: k_pyramid's v_perm selector, bytes relative to s0 */
+            P.pyr_kblob.push_back((uint32_t)(lo - origin) | ((uint32_t)(hi - lo) << 16));
+          }
+          else { /* columns 1..3: source bytes relative to s0, as v_perm selectors (0x0C: a zero byte) */
             P.pyr_blob.push_back((uint32_t)(lo - glo) | 0x0C00u | ((uint32_t)(hi - glo) << 16) | 0x0C000000u);
-          P.pyr_blob.push_back((uint32_t)(uint16_t)cf[0] | ((uint32_t)(uint16_t)cf[1] << 16));
+            P.pyr_kblob.push_back(0x0Cu | ((uint32_t)(lo - glo) << 8) | 0x0C0000u | ((uint32_t)(hi - glo) << 24));
+          }
+          const uint32_t cpair = (uint32_t)(uint16_t)cf[0] | ((uint32_t)(uint16_t)cf[1] << 16);
+          P.pyr_blob.push_back(cpair);
+          P.pyr_kblob.push_back(isx ? cpair << 4 : cpair); /* 16*a <= 32768: stays in its half */
           ++n;
         }
       }
-      while (n & 1) { P.pyr_blob.push_back(0); P.pyr_blob.push_back(0); ++n; } /* 16-B pad */
+      while (n & 1) { /* 16-B pad */
+        P.pyr_blob.insert(P.pyr_blob.end(), 2, 0u);
+        P.pyr_kblob.insert(P.pyr_kblob.end(), 2, 0u);
+        ++n;
+      }
       maxn = std::max(maxn, n);
     }
     P.pyr_bo.push_back((int)(P.pyr_blob.size() / 2));
@@ -343,6 +362,7 @@ static int plan_pyramid(Plan& P) {
   P.pyr_xs.clear();
   P.pyr_ys.clear();
   P.pyr_blob.clear();
+  P.pyr_kblob.clear();
   P.pyr_bo.clear();
   std::vector<int> uniq;
   for (int l = 0; l < (int)P.levels.size(); ++l)

@@ -45,7 +45,9 @@ struct Plan {
   std::vector<int32_t> pyr_xs;   /* {clo, chi, plo, phi} quads */
   std::vector<int32_t> pyr_ys;
   std::vector<uint32_t> pyr_blob; /* LUT blobs (pairs of u32 = uint2 entries) */
-  std::vector<int32_t> pyr_bo;    /* blob start offsets (uint2 units), per segment ntx+1, nty+1 */
+  std::vector<uint32_t> pyr_kblob; /* the same entries as k_pyramid reads them (the uploaded table): column
+                                    * selectors with the source bytes placed high, column coefficients x16 */
+  std::vector<int32_t> pyr_bo;    /* blob start offsets (uint2 units) into either form, per segment ntx+1, nty+1 */
   long long pyr_bytes = 0, blur_bytes = 0, nslots = 0, qk_elems = 0;
   int ncells = 0, kcap = 0;
   int qt_smax = 0;     /* max DistributeOctTree splittable list length */

@@ -265,18 +265,22 @@ __global__ __launch_bounds__(256) void k_pyramid(const uint8_t* __restrict__ fra
         // (scale < 2: sx1[3] - sx[0] <= 7, checked by the planner): two
         // v_alignbyte of three LDS dwords per source row (one unaligned
         // ds_read_b64 instead: 0.685 -> 1.20 ms, c4), then one v_perm (bytes
-        // sx, sx1 -> u16 pair) and one v_dot2_u32_u16 with the (a0, a1) pair
-        // per column: D = S[sx]*a0 + S[sx1]*a1
-        // blob (geometry.cpp build_blobs): column 0 of the group holds
-        // s0 | (sx1 - s0) << 16, columns 1..3 their v_perm selectors
-        // relative to s0; .y = a0 | a1 << 16, both in [0, 2048]
+        // sx, sx1 -> the high bytes of a u16 pair, zero below: S << 8) and
+        // one v_dot2_u32_u16 with the (16*a0, 16*a1) pair per column:
+        // X = (S[sx] << 8)*16*a0 + (S[sx1] << 8)*16*a1 = 4096*D, so that
+        // D >> 4 is X's high word (pyr_arith.h; a0 + a1 == 2048, checked by
+        // the planner: X <= 255*2048*4096 < 2^32, 16*a <= 32768 fits a half)
+        // blob (geometry.cpp build_blobs, the kernel's form): column 0 of the
+        // group holds s0 | (sx1 - s0) << 16, columns 1..3 their v_perm
+        // selectors relative to s0 (bytes 1 / 3; 0x0C = zero in bytes 0 / 2);
+        // .y = 16*a0 | 16*a1 << 16
         uint32_t hsel[4], hcoef[4];
         uint32_t hbase, hsh;
         {
           const uint2 e0 = xl[xo + 4 * cg];
           hbase = (e0.x & 0xFFFCu) + lds_addr(plds);  // LDS byte address of the window's first dword
           hsh = e0.x & 3u;
-          hsel[0] = (e0.x & 0xFFFF0000u) | 0x0C000C00u;
+          hsel[0] = ((e0.x << 8) & 0xFF000000u) | 0x000C000Cu;  // bytes 0 and sx1 - s0 (< 8), placed high
           hcoef[0] = e0.y;
 #pragma unroll
           for (int k = 1; k < 4; ++k) {
@@ -306,16 +310,13 @@ __global__ __launch_bounds__(256) void k_pyramid(const uint8_t* __restrict__ fra
           rv += R;
           rw = __builtin_amdgcn_readfirstlane(rw + R);  // a separate scalar trip counter (opaque: not folded into rv)
           const uint2 e = *reinterpret_cast<const uint2*>(plds + (ylb + 8u * r));
-          // SDWA halves of the entry: hbase + off0 / off1, b0 << 12 / b1 << 12
-          // (the u24 multiply reads the low 24 bits: b0's shift needs no mask)
-          uint32_t a0, a1, bs0, bs1;
+          // SDWA halves of the entry: hbase + off0 / off1 here, b0 / b1 (e.y's
+          // words) as operand selects of the vertical multiplies below
+          uint32_t a0, a1;
           asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0"
               : "=v"(a0) : "v"(hbase), "v"(e.x));
           asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1"
               : "=v"(a1) : "v"(hbase), "v"(e.x));
-          bs0 = e.y << 12;
-          asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1"
-              : "=v"(bs1) : "v"(12u), "v"(e.y));
           typedef const __attribute__((address_space(3))) uint32_t* lds_u32p;
           const lds_u32p R0 = (lds_u32p)(size_t)a0, R1 = (lds_u32p)(size_t)a1;
           const uint32_t lo0 = __builtin_amdgcn_alignbyte(R0[1], R0[0], hsh);
@@ -325,27 +326,34 @@ __global__ __launch_bounds__(256) void k_pyramid(const uint8_t* __restrict__ fra
           uint32_t v[4];
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            // vertical: ((b*(D>>4))>>16) == mulhi_u24(b << 12, D & ~15)
-            // (b <= 2048, D <= 255*2048: both operands < 2^24, exact)
-            const uint32_t d0 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(hi0, lo0, hsel[k])),
+            const uint32_t x0 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(hi0, lo0, hsel[k])),
                                                        as_us2(hcoef[k]), 0u, false);
-            const uint32_t d1 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(hi1, lo1, hsel[k])),
+            const uint32_t x1 = __builtin_amdgcn_udot2(as_us2(__builtin_amdgcn_perm(hi1, lo1, hsel[k])),
                                                        as_us2(hcoef[k]), 0u, false);
-            // (operands from LDS: the 24-bit form is spelled out, the
-            // compiler would emit the quarter-rate v_mul_hi_u32)
+            // vertical, on word boundaries (pyr_arith.h): x = 4096*D, so
+            // D >> 4 is x's high word and b0 / b1 are e.y's words, all read
+            // by SDWA selects: t = b*(D>>4) (b <= 2048, D>>4 <= 32640: both
+            // operands < 2^24 and t <= 66846720, the 24-bit multiply is
+            // exact), then (t0 >> 16) + (t1 >> 16) as the sum of the high
+            // words.  (Spelled out: the compiler would extract the words
+            // with extra instructions or emit the quarter-rate v_mul_lo_u32)
             uint32_t t0, t1;
-            asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(t0) : "v"(bs0), "v"(d0 & 0xFFFFF0u));
-            asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(t1) : "v"(bs1), "v"(d1 & 0xFFFFF0u));
-            v[k] = t0 + t1 + 2u;  // < 1024
+            asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_1"
+                : "=v"(t0) : "v"(e.y), "v"(x0));
+            asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1"
+                : "=v"(t1) : "v"(e.y), "v"(x1));
+            asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_1"
+                : "=v"(v[k]) : "v"(t0), "v"(t1));  // <= 1020
           }
-          // (v >> 2) of the four columns as bytes: two u16 pairs shifted as
-          // whole dwords (v < 1024: the pair's high value lands whole in
-          // bits 16..23), then one v_perm
+          // ((v + 2) >> 2) of the four columns as bytes: two u16 pairs,
+          // rounded and shifted as whole dwords (v + 2 < 1024: no carry
+          // crosses a half, and the pair's high value lands whole in bits
+          // 16..23), then one v_perm
           uint32_t p01, p23;
           asm("v_lshl_or_b32 %0, %1, 16, %2" : "=v"(p01) : "v"(v[1]), "v"(v[0]));
           asm("v_lshl_or_b32 %0, %1, 16, %2" : "=v"(p23) : "v"(v[3]), "v"(v[2]));
-          p01 >>= 2;
-          p23 >>= 2;
+          p01 = (p01 + 0x00020002u) >> 2;
+          p23 = (p23 + 0x00020002u) >> 2;
           const uint32_t packed = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
           *reinterpret_cast<uint32_t*>(plds + (lbase + __umul24(r, dpitch))) = packed;
           // every computed row, also the ones another tile owns: computed

@@ -192,7 +192,9 @@ struct BriefArgs {
  * for every level s = 1..nl and every computed column c in [dax, dax+4*ncg)
  * (row in [clo, chi)); column sources relative to the LDS origin of level
  * s-1's region, row sources as LDS byte offsets of the two source rows
- * (ping-pong buffer + row * lpitch[s-1]); blobs are padded to 16 B */
+ * (ping-pong buffer + row * lpitch[s-1]); blobs are padded to 16 B.  The
+ * column entries k_pyramid reads are in its word-aligned form (geometry.cpp
+ * build_blobs, Plan::pyr_kblob) */
 struct PyrSeg {
   int nl;
   int area;           /* 1: one exact-2x level by INTER_AREA (k_pyr_area2; nl = 1, no tiling) */
