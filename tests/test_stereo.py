@@ -5,6 +5,8 @@ gives that disparity, an empty right frame gives no matches, the median
 filter keeps SADs below 1.5f*1.4f*median -- and the golden fixture.
 GPU: orbx_stereo_match / orbs_plan_match vs the oracle, bit-exact on
 mvuRight and mvDepth (IEEE float bits) and on the kept-match count.
+Planted edge cases, the multi-keypoint wave loop and tall frames:
+test_stereo_planted.py (CPU) and test_stereo_gpu_edges.py (GPU).
 """
 import os
 
