@@ -1,43 +1,20 @@
 // api_proj.hip -- C ABI of the frame grid + ORBmatcher::SearchByProjection
-// (query form, /root/reference/src/ORBmatcher.cc:19-61,732-818,820-894).
+// (query form, src/ORBmatcher.cc:19-61,732-818,820-894).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "../../include/orbx.h"
 #include "call_arena.h"
+#include "proj_internal.h"
 
-namespace orbx {
-struct ProjFrame {
-  int n;
-  float minX, minY, wInv, hInv;
-};
-struct ProjProblem {  // kernels_proj.hip
-  ProjFrame F;
-  const orbx_keypoint* keys;
-  const uint8_t* desc;
-  const float* uright;
-  const uint8_t* occupied;
-  const orbx_query_proj* qs;
-  const uint8_t* qdesc;
-  int nq;
-  int32_t* match;
-  int* nmatches;
-  int* cell_off;
-  int* cell_feat;
-  uint32_t* cand;
-  int* ncand;
-};
+namespace orbx {  // kernels_proj.hip
 __global__ void k_grid_build(const ProjProblem*);
 __global__ void k_proj_cand(const ProjProblem*, int);
 __global__ void k_proj_resolve(const ProjProblem*, int, float, int, int);
 }  // namespace orbx
 
 using namespace orbx;
-
-#define PJ_T 8
-#define PJ_MAXN 8192
-#define PG_CELLS (64 * 48)
 
 static ProjFrame proj_frame(const orbx_proj_frame* F) {
   ProjFrame PF;

@@ -14,42 +14,12 @@
 
 #include "../../include/orbx.h"
 #include "orbm_device.h"
+#include "proj_internal.h"
 #include "wave_ops.h"
 
 namespace orbx {
 
-#define PG_COLS 64 /* FRAME_GRID_COLS (include/Frame.h:18) */
-#define PG_ROWS 48 /* FRAME_GRID_ROWS (include/Frame.h:17) */
-#define PG_CELLS (PG_COLS * PG_ROWS)
-#define PJ_T 8     /* candidates kept per query */
-#define PJ_MAXN 8192
 #define PJ_DEVERR 16
-
-struct ProjFrame {
-  int n;
-  float minX, minY, wInv, hInv;
-};
-
-// one SearchByProjection call: the frame, its queries, outputs and grid /
-// candidate scratch (device pointers).  The drop-in call launches one; the
-// batched plan (orbm_proj_plan_search) launches many at once, problem =
-// blockIdx.y (candidates) or blockIdx.x (grid, walk).
-struct ProjProblem {
-  ProjFrame F;
-  const orbx_keypoint* keys;
-  const uint8_t* desc;
-  const float* uright;
-  const uint8_t* occupied;
-  const orbx_query_proj* qs;
-  const uint8_t* qdesc;
-  int nq;
-  int32_t* match;
-  int* nmatches;
-  int* cell_off;   // PG_CELLS + 1
-  int* cell_feat;  // n
-  uint32_t* cand;  // nq x PJ_T
-  int* ncand;      // nq
-};
 
 // one workgroup: cells of every feature, ix-major stable order by an LDS
 // bitonic sort of (cell << 16 | index) keys (index order inside a cell, as
