@@ -26,8 +26,9 @@ extern "C" {
  * orbx_proj_problem and the orbm_proj_plan_* / orbm_search_by_bow_kf_frame
  * entry points added (round 5).  orbx_tri_frame and
  * orbm_search_for_triangulation, and orbx_kf_frame / orbx_kf_query and
- * orbm_keyframe_search, are additive (no existing struct or entry point
- * changes), so the version stays 2. */
+ * orbm_keyframe_search, and orbx_init_pair and
+ * orbm_search_for_initialization, are additive (no existing struct or entry
+ * point changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
 /* status codes */
@@ -384,6 +385,55 @@ typedef struct {
 int orbm_keyframe_search(int nprob, const orbx_kf_frame* kf, const orbx_kf_query* q,
                          const int32_t* qoff /* nprob + 1 */, const uint8_t* qdesc, int npool,
                          int device, int32_t* best_idx, int32_t* best_dist);
+
+/* One ORBmatcher::SearchForInitialization call (src/ORBmatcher.cc:197-276):
+ * F1 = the initial frame, F2 = the current one. */
+typedef struct {
+  orbx_kf_frame f1, f2;   /* mvKeysUn (pt, octave, angle), mDescriptors; grid constants of f2 only */
+  float* prev_matched;    /* in/out, 2 * f1.n: vbPrevMatched (x, y)                                */
+  int32_t* match12;       /* in/out, f1.n: vnMatches12 as the previous call left it                 */
+} orbx_init_pair;
+
+/* ORBmatcher::SearchForInitialization (src/ORBmatcher.cc:197-276), the
+ * monocular bootstrap of Tracking::MonocularInitialization, batched: npair
+ * independent pairs (streams bootstrapping at once) in one upload, one set of
+ * launches and one download; npair = 1 is the member function.
+ * Per pair, for i1 ascending: a row with f1 octave > 0 is skipped; a row with
+ * a negative octave is not, and searches every octave of f2.  Candidates are
+ * Frame::GetFeaturesInArea(prev_matched[i1], (float)window_size, octave,
+ * octave) on f2 (src/Frame.cc:307-358: the 64 x 48 grid filled by PosInGrid's
+ * round() in index order, the floor / ceil cell bounds with their clamps and
+ * early returns, cells visited ix then iy then the cell's list, the level
+ * gate, the strict box test).  Over them in visiting order only candidates
+ * closer than their feature's current holder (dist < vMatchedDistance[i2])
+ * take part: best = the first strict minimum, second best = the second
+ * smallest distance as a multiset (it may equal best).  Accepted when best <=
+ * TH_LOW (50) and best < (float)second * nnratio; an accepted row takes the
+ * feature away from its holder (the holder's match12 becomes -1).  With
+ * check_ori the accepted rows, displaced ones included, vote in the 30-bin
+ * rotation histogram (bin = round(rot / 30), 30 wraps to 0) and rows outside
+ * the three fullest bins that still hold a match are reset to -1 (not the -2
+ * of orbm_search_by_bow: match12 feeds the next call).
+ * match12 is not cleared (the reference's resize(n, -1) keeps the caller's
+ * entries): a row not accepted by this call keeps its value, nmatches[p]
+ * counts this call's matches only, and prev_matched[i1] = f2.keys[match12[i1]]
+ * .pt for every row >= 0, the kept ones included.
+ * Host pointers; synchronous; safe from several threads.  ORBX_ERR_ARG for
+ * npair < 0, a null pointer where a count is positive, a non-finite coordinate
+ * in prev_matched or f2.keys, with check_ori a key angle outside [0, 360] or
+ * non-finite (the bin would leave the histogram), and a row that ends the call
+ * holding an entry >= f2.n (the reference reads out of range there; found on
+ * the device, reported after the download).  ORBX_ERR_UNSUPPORTED for f1.n or
+ * f2.n > 8192.  On any error no output is written.  npair == 0, n == 0 and a
+ * pair without level-0 rows are valid. */
+int orbm_search_for_initialization(int npair, const orbx_init_pair* pairs, int window_size,
+                                   float nnratio, int check_ori, int device, int* nmatches /* npair */);
+/* the same call; nrescan (npair, may be NULL) receives per pair the number of
+ * rows whose step of the ordered walk had to scan its window a second time
+ * (DESIGN.md §15): a diagnostic for tools and tests. */
+int orbm_search_for_initialization_stats(int npair, const orbx_init_pair* pairs, int window_size,
+                                         float nnratio, int check_ori, int device, int* nmatches,
+                                         int* nrescan);
 
 /* ORBmatcher::DescriptorDistance (src/ORBmatcher.cc:896-908), batched on the
  * device: dist[i] = Hamming(a + 32*ia[i], b + 32*ib[i]); host pointers. */

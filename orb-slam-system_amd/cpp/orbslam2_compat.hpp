@@ -15,7 +15,8 @@
 //     public mvImagePyramid);
 //   * ORB_SLAM2::ORBmatcher with ORBmatcher.h's DescriptorDistance and the
 //     two SearchByBoW overloads (include/ORBmatcher.h:20-45),
-//     SearchForTriangulation (:51-52), SearchBySim3 (:56) and both Fuse forms
+//     SearchForInitialization (:48), SearchForTriangulation (:51-52),
+//     SearchBySim3 (:56) and both Fuse forms
 //     (:59, :62) as templates over the caller's KeyFrame / MapPoint / Frame
 //     classes, reading exactly the members the reference reads
 //     (GetMapPointMatches, GetMapPoint, isBad, mvKeysUn, mFeatVec,
@@ -369,8 +370,9 @@ class ORBextractor {
 };
 
 // ORB_SLAM2::ORBmatcher: DescriptorDistance, SearchByBoW,
-// SearchForTriangulation, SearchBySim3 and Fuse (include/ORBmatcher.h:20-62;
-// src/ORBmatcher.cc:88-119,278-366,368-467,504-730,896-908).
+// SearchForInitialization, SearchForTriangulation, SearchBySim3 and Fuse
+// (include/ORBmatcher.h:20-62;
+// src/ORBmatcher.cc:88-119,197-276,278-366,368-467,504-730,896-908).
 class ORBmatcher {
  public:
   static const int TH_LOW = 50, TH_HIGH = 100, HISTO_LENGTH = 30;  // ORBmatcher.cc:13-15
@@ -685,7 +687,74 @@ class ORBmatcher {
     return nMatches;
   }
 
+  // SearchForInitialization(Frame&, Frame&, vector<cv::Point2f>&,
+  // vector<int>&, int windowSize=10) (include/ORBmatcher.h:48;
+  // src/ORBmatcher.cc:197-276) on the device.  FR: the reference's Frame
+  // (mvKeysUn, mDescriptors, mnMinX, mnMinY, mfGridElementWidthInv,
+  // mfGridElementHeightInv).  vnMatches12 is resized as :199 does, without
+  // clearing: Tracking hands in the same mvIniMatches while an initializer
+  // lives, and rows this call does not match keep their entries.
+  template <class FR>
+  int SearchForInitialization(FR& F1, FR& F2, std::vector<cv::Point2f>& vbPrevMatched,
+                              std::vector<int>& vnMatches12, int windowSize = 10) {
+    orbx_init_pair P = init_pair(F1, F2, vbPrevMatched, vnMatches12);
+    int n = 0;
+    orbx_throw(orbm_search_for_initialization(1, &P, windowSize, mfNNratio, mbCheckOrientation ? 1 : 0, 0, &n),
+               "SearchForInitialization");
+    return n;
+  }
+
+  // batched form (no counterpart in the reference): pair i = (*vpF1[i],
+  // *vpF2[i]) with its own vbPrevMatched / vnMatches12, for several streams
+  // bootstrapping at once: one upload, one set of launches, one download.
+  // Returns the nmatches of every pair.
+  template <class FR>
+  std::vector<int> SearchForInitialization(const std::vector<FR*>& vpF1, const std::vector<FR*>& vpF2,
+                                           std::vector<std::vector<cv::Point2f> >& vvbPrevMatched,
+                                           std::vector<std::vector<int> >& vvnMatches12, int windowSize = 10) {
+    const size_t np = vpF1.size();
+    if (vpF2.size() != np || vvbPrevMatched.size() != np || vvnMatches12.size() != np)
+      orbx_throw(ORBX_ERR_ARG, "SearchForInitialization");
+    std::vector<orbx_init_pair> P(np);
+    for (size_t i = 0; i < np; ++i) P[i] = init_pair(*vpF1[i], *vpF2[i], vvbPrevMatched[i], vvnMatches12[i]);
+    std::vector<int> n(np ? np : 1, 0);
+    orbx_throw(orbm_search_for_initialization((int)np, P.data(), windowSize, mfNNratio,
+                                              mbCheckOrientation ? 1 : 0, 0, n.data()),
+               "SearchForInitialization");
+    n.resize(np);
+    return n;
+  }
+
  protected:
+  template <class FR>
+  static orbx_kf_frame init_frame(FR& F) {
+    orbx_kf_frame f;
+    f.n = (int)F.mvKeysUn.size();
+    f.keys = reinterpret_cast<const orbx_keypoint*>(F.mvKeysUn.data());
+    f.desc = F.mDescriptors.data;
+    f.min_x = F.mnMinX;
+    f.min_y = F.mnMinY;
+    f.grid_w_inv = F.mfGridElementWidthInv;
+    f.grid_h_inv = F.mfGridElementHeightInv;
+    return f;
+  }
+  template <class FR>
+  static orbx_init_pair init_pair(FR& F1, FR& F2, std::vector<cv::Point2f>& vbPrevMatched,
+                                  std::vector<int>& vnMatches12) {
+    static_assert(sizeof(cv::Point2f) == 2 * sizeof(float) && sizeof(int) == sizeof(int32_t) &&
+                      sizeof(cv::KeyPoint) == sizeof(orbx_keypoint),
+                  "vbPrevMatched / vnMatches12 / mvKeysUn are handed over in place");
+    vnMatches12.resize(F1.mvKeysUn.size(), -1);  // :199
+    // the reference indexes vbPrevMatched[i1] unchecked
+    if (vbPrevMatched.size() < F1.mvKeysUn.size()) orbx_throw(ORBX_ERR_ARG, "SearchForInitialization");
+    orbx_init_pair P;
+    P.f1 = init_frame(F1);
+    P.f2 = init_frame(F2);
+    P.prev_matched = reinterpret_cast<float*>(vbPrevMatched.data());
+    P.match12 = reinterpret_cast<int32_t*>(vnMatches12.data());
+    return P;
+  }
+
   // the queries of one orbm_keyframe_search call: begin(KF) .. add(..)* ..
   // end() per problem, then run()
   struct KfSearch {

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/orbx.h"
+#include "grid_device.h"
 #include "orbm_device.h"
 #include "proj_internal.h"
 #include "wave_ops.h"
@@ -75,24 +76,6 @@ __global__ __launch_bounds__(1024) void k_grid_build(const ProjProblem* __restri
   }
   for (int i = tid; i < P; i += 1024)
     if (sk[i] != 0xFFFFFFFFu) cell_feat[i] = (int)(sk[i] & 0xFFFFu);
-}
-
-// GetFeaturesInArea cell bounds (:312-326); false = empty
-__device__ __forceinline__ bool area_cells(const ProjFrame& F, float x, float y, float r,
-                                           int* x0, int* x1, int* y0, int* y1) {
-  const int mincx = (int)floorf((x - F.minX - r) * F.wInv);
-  *x0 = mincx > 0 ? mincx : 0;
-  if (*x0 >= PG_COLS) return false;
-  const int maxcx = (int)ceilf((x - F.minX + r) * F.wInv);
-  *x1 = maxcx < PG_COLS - 1 ? maxcx : PG_COLS - 1;
-  if (*x1 < 0) return false;
-  const int mincy = (int)floorf((y - F.minY - r) * F.hInv);
-  *y0 = mincy > 0 ? mincy : 0;
-  if (*y0 >= PG_ROWS) return false;
-  const int maxcy = (int)ceilf((y - F.minY + r) * F.hInv);
-  *y1 = maxcy < PG_ROWS - 1 ? maxcy : PG_ROWS - 1;
-  if (*y1 < 0) return false;
-  return true;
 }
 
 // candidate filter of one feature (level, box, stereo gate) and its key

@@ -7,6 +7,7 @@ reference interfaces for tests and the benchmark:
   search_by_bow  ORBmatcher::SearchByBoW(KF, KF) (/root/reference/src/ORBmatcher.cc:278-366)
   search_for_triangulation  ORBmatcher::SearchForTriangulation, batched (ORBmatcher.cc:368-467)
   keyframe_search  the search of ORBmatcher::Fuse / SearchBySim3, batched (ORBmatcher.cc:532-551)
+  search_for_initialization  ORBmatcher::SearchForInitialization, batched (ORBmatcher.cc:197-276)
   compute_stereo_matches  Frame::ComputeStereoMatches (/root/reference/src/Frame.cc:446-620)
   descriptor_distance_batch  ORBmatcher::DescriptorDistance (ORBmatcher.cc:896-908)
   Plan / MatchPlan  batched device-resident throughput path (bench.py)
@@ -64,6 +65,7 @@ EXPORTED = [
     "orbm_proj_plan_create", "orbm_proj_plan_destroy", "orbm_proj_plan_search",
     "orbm_compute_distinctive_descriptors", "orbx_undistort_keypoints", "orbx_selftest_sincos",
     "orbx_selftest_sincos_range", "orbm_search_for_triangulation", "orbm_keyframe_search",
+    "orbm_search_for_initialization", "orbm_search_for_initialization_stats",
 ]
 
 
@@ -138,6 +140,14 @@ KF_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("radius", "<f4"), ("leve
                            ("desc", "<i4")])
 assert KF_QUERY_DTYPE.itemsize == ctypes.sizeof(KfQuery) == 20
 
+class InitPair(ctypes.Structure):  # orbx_init_pair
+    _fields_ = [("f1", KfFrame), ("f2", KfFrame), ("prev_matched", ctypes.c_void_p),
+                ("match12", ctypes.c_void_p)]
+
+
+# k_init_cand's list length per row and the feature limit (csrc/init_internal.h)
+INIT_T, INIT_MAXN = 8, 8192
+
 # k_kfwin_search's lanes per query and k_kfwin_grid's feature limit
 # (csrc/kfwin_internal.h)
 KFW_G, KFW_MAXN = 8, 8192
@@ -184,6 +194,8 @@ _sig = {
     "orbm_search_by_bow_kf_frame": (I, [P, P, F, I, I, P, P]),
     "orbm_search_for_triangulation": (I, [P, I, P, P, I, I, I, P, P]),
     "orbm_keyframe_search": (I, [I, P, P, P, P, I, I, P, P]),
+    "orbm_search_for_initialization": (I, [I, P, I, F, I, I, P]),
+    "orbm_search_for_initialization_stats": (I, [I, P, I, F, I, I, P, P]),
     "orbm_descriptor_distance_batch": (I, [P, I, P, I, P, P, I, I, P]),
     "orbm_plan_create": (I, [I, I, I, I, P]),
     "orbm_plan_destroy": (I, [P]),
@@ -570,6 +582,47 @@ def keyframe_search(kfs, queries, qdesc, device=0):
     _check(_lib.orbm_keyframe_search(nprob, ctypes.cast(arr, ctypes.c_void_p), _p(q), _p(qoff), _p(qd),
                                      len(qd), device, _p(bi), _p(bd)), "orbm_keyframe_search")
     return [(bi[qoff[p]:qoff[p + 1]].copy(), bd[qoff[p]:qoff[p + 1]].copy()) for p in range(nprob)]
+
+
+def init_pair_struct(pair, keep):
+    """orbx_init_pair of dict(f1, f2, prev_matched, match12): f1 / f2 are frame
+    dicts (kf_struct; f1's grid constants are not read and may be absent),
+    prev_matched float32[n1, 2] and match12 int32[n1].  Both arrays are copied
+    (the call writes into the copies), appended to keep and returned."""
+    f1 = dict(min_x=0.0, min_y=0.0, grid_w_inv=0.0, grid_h_inv=0.0)
+    f1.update(pair["f1"])
+    a, b = kf_struct(f1, keep), kf_struct(pair["f2"], keep)
+    prev = np.array(pair["prev_matched"], np.float32).reshape(-1, 2)
+    m12 = np.array(pair["match12"], np.int32).reshape(-1)
+    if len(prev) != a.n or len(m12) != a.n:
+        raise OrbxError(ERR_ARG, "prev_matched and match12 need one row per F1 feature")
+    keep.extend([prev, m12])
+    return InitPair(a, b, _p(prev), _p(m12)), prev, m12
+
+
+def search_for_initialization(pairs, window_size=100, nnratio=0.9, check_ori=True, device=0, stats=False):
+    """ORBmatcher::SearchForInitialization (orbm_search_for_initialization),
+    batched over independent pairs (init_pair_struct dicts): one upload, one
+    set of launches, one download.  Returns per pair (match12 int32[n1],
+    prev_matched float32[n1, 2], nmatches), the inputs left untouched; hand
+    match12 and prev_matched back in for the next frame, as Tracking keeps
+    mvIniMatches and mvbPrevMatched.  stats=True appends the number of rows
+    whose walk step scanned its window again."""
+    keep, out = [], []
+    npair = len(pairs)
+    arr = (InitPair * max(npair, 1))()
+    for p, pair in enumerate(pairs):
+        arr[p], prev, m12 = init_pair_struct(pair, keep)
+        out.append((m12, prev))
+    nm = np.zeros(max(npair, 1), np.int32)
+    resc = np.zeros(max(npair, 1), np.int32)
+    args = (npair, ctypes.cast(arr, ctypes.c_void_p), int(window_size), float(nnratio), 1 if check_ori else 0,
+            device, _p(nm))
+    if stats:
+        _check(_lib.orbm_search_for_initialization_stats(*args, _p(resc)), "orbm_search_for_initialization")
+        return [(m, pv, int(nm[p]), int(resc[p])) for p, (m, pv) in enumerate(out)]
+    _check(_lib.orbm_search_for_initialization(*args), "orbm_search_for_initialization")
+    return [(m, pv, int(nm[p])) for p, (m, pv) in enumerate(out)]
 
 
 def descriptor_distance_batch(a, b, ia, ib, device=0):
