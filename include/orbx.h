@@ -27,8 +27,9 @@ extern "C" {
  * entry points added (round 5).  orbx_tri_frame and
  * orbm_search_for_triangulation, and orbx_kf_frame / orbx_kf_query and
  * orbm_keyframe_search, and orbx_init_pair and
- * orbm_search_for_initialization, are additive (no existing struct or entry
- * point changes), so the version stays 2. */
+ * orbm_search_for_initialization, and the debug entry points
+ * orbx_debug_live_resources / orbx_debug_fail_acquire, are additive (no
+ * existing struct or entry point changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
 /* status codes */
@@ -198,6 +199,17 @@ int orbx_plan_fast_dense_strips(orbx_plan* plan, int* fast_dense_strips);
  * strength-map overflow path runs on ordinary frames; ccap < 0 restores the
  * planner's own length.  Process-global; results are unchanged either way. */
 int orbx_debug_set_fast_ccap(int ccap);
+/* Debugging: the device buffers, pinned host buffers, streams and events
+ * (counts[0..3]) that the handles of this library hold at the moment, over
+ * the whole process.  A handle that was destroyed has given all of its own
+ * back.  The per-call workspaces of the synchronous entry points are pooled
+ * for the life of the process and are not counted. */
+int orbx_debug_live_resources(int counts[4]);
+/* Testing only: from now on the `nth` acquisition of such a resource on the
+ * calling thread fails (the entry point returns ORBX_ERR_HIP) without a call
+ * into the HIP runtime; the ones before and after it proceed.  nth <= 0
+ * disarms. */
+int orbx_debug_fail_acquire(int nth);
 
 /* Kernel-path options of a plan (default 0 = automatic; persistent).  Every
  * path gives bit-identical results; they differ in speed only.

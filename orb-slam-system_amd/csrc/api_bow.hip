@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -31,48 +32,30 @@ using namespace orbx;
 struct orbv_vocab {
   int device = 0;
   int k = 0, L = 0, scoring = 0, weighting = 0, nnodes = 0, nwords = 0;
-  int* d_cbeg = nullptr;
-  int* d_cid = nullptr;
-  uint8_t* d_cdesc = nullptr;
-  uint32_t* d_word = nullptr;
-  double* d_weight = nullptr;
-  int* d_err = nullptr;
-  BowRes* d_res = nullptr;
+  DevBuf<int> d_cbeg, d_cid;
+  DevBuf<uint8_t> d_cdesc;
+  DevBuf<uint32_t> d_word;
+  DevBuf<double> d_weight;
+  DevBuf<int> d_err;
+  DevBuf<BowRes> d_res;
   size_t res_cap = 0;
   /* outgrown d_res buffers: launches on callers' streams may still read
    * them, so they are freed with the vocabulary, not on growth (no device
    * synchronisation on the transform path) */
-  std::vector<void*> retired;
-  /* host drop-in staging (one frame) */
-  uint8_t* d_desc1 = nullptr;
-  int* d_cnt1 = nullptr;
-  uint32_t *d_bw = nullptr, *d_fn = nullptr, *d_fo = nullptr, *d_ff = nullptr;
-  double* d_bv = nullptr;
-  int* d_n2 = nullptr;
-  int cap1 = 0;
-  hipStream_t stream = nullptr;
+  std::vector<DevBuf<BowRes>> retired;
+  /* host drop-in staging (one frame of up to cap features): replaced whole
+   * when a frame outgrows it */
+  struct Staging {
+    DevBuf<uint8_t> d_desc;
+    DevBuf<int> d_cnt;
+    DevBuf<uint32_t> d_bw, d_fn, d_fo, d_ff;
+    DevBuf<double> d_bv;
+    DevBuf<int> d_n2;
+    int cap = 0;
+  } one;
+  Stream stream;
+  ~orbv_vocab() { hipSetDevice(device); }
 };
-
-static void vocab_free(orbv_vocab* v) {
-  if (!v) return;
-  hipSetDevice(v->device);
-  void* bufs[] = {v->d_cbeg, v->d_cid, v->d_cdesc, v->d_word, v->d_weight, v->d_err, v->d_res,
-                  v->d_desc1, v->d_cnt1, v->d_bw, v->d_fn, v->d_fo, v->d_ff, v->d_bv, v->d_n2};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  for (void* b : v->retired) hipFree(b);
-  if (v->stream) hipStreamDestroy(v->stream);
-  delete v;
-}
-
-template <typename T>
-static int upload_vec(T** dst, const std::vector<T>& h) {
-  const size_t n = std::max<size_t>(h.size(), 1);
-  if (hipMalloc((void**)dst, n * sizeof(T)) != hipSuccess) return ORBX_ERR_HIP;
-  if (!h.empty() && hipMemcpy(*dst, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-    return ORBX_ERR_HIP;
-  return ORBX_OK;
-}
 
 extern "C" int orbv_vocab_create(int k, int L, int scoring, int weighting, int nrec,
                                  const int32_t* parent, const int32_t* is_leaf,
@@ -109,25 +92,20 @@ extern "C" int orbv_vocab_create(int k, int L, int scoring, int weighting, int n
   }
   for (int i = 0; i < n; ++i)
     if (cnt[i] > 65535) return ORBX_ERR_UNSUPPORTED;
-  orbv_vocab* v = new orbv_vocab();
+  std::unique_ptr<orbv_vocab> v(new orbv_vocab());
   v->device = device;
   v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting;
   v->nnodes = n;
   v->nwords = nwords;
-  if (hipSetDevice(device) != hipSuccess || upload_vec(&v->d_cbeg, cbeg) ||
-      upload_vec(&v->d_cid, cid) || upload_vec(&v->d_cdesc, cdesc) ||
-      upload_vec(&v->d_word, word) || upload_vec(&v->d_weight, w) ||
-      hipMalloc((void**)&v->d_err, 16) != hipSuccess || hipMemset(v->d_err, 0, 16) != hipSuccess ||
-      hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) != hipSuccess) {
-    vocab_free(v);
+  if (hipSetDevice(device) != hipSuccess || upload(v->d_cbeg, cbeg, true) ||
+      upload(v->d_cid, cid, true) || upload(v->d_cdesc, cdesc, true) ||
+      upload(v->d_word, word, true) || upload(v->d_weight, w, true) ||
+      v->d_err.alloc(4) || hipMemset(v->d_err, 0, 16) != hipSuccess || v->stream.create())
     return ORBX_ERR_HIP;
-  }
   if (hipFuncSetAttribute((const void*)k_bow_assemble, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          ORBV_MAX_SORT * 8) != hipSuccess) {
-    vocab_free(v);
+                          ORBV_MAX_SORT * 8) != hipSuccess)
     return ORBX_ERR_HIP;
-  }
-  *out = v;
+  *out = v.release();
   return ORBX_OK;
 }
 
@@ -210,7 +188,7 @@ extern "C" int orbv_vocab_load_text(const char* path, int device, orbv_vocab** o
 }
 
 extern "C" int orbv_vocab_destroy(orbv_vocab* v) {
-  vocab_free(v);
+  delete v;
   return ORBX_OK;
 }
 
@@ -249,10 +227,9 @@ extern "C" int orbv_transform_batch(orbv_vocab* v, int nframes, const uint8_t* d
     /* geometric growth: the retired buffers (which launches on other
      * streams may still read) stay below twice the current one */
     const size_t cap = std::max(need, v->res_cap + v->res_cap / 2);
-    if (v->d_res) v->retired.push_back(v->d_res);
-    v->d_res = nullptr;
+    if (v->d_res) v->retired.push_back(std::move(v->d_res));
     v->res_cap = 0;
-    ORBX_TRY(hipMalloc((void**)&v->d_res, cap * sizeof(BowRes)));
+    if (v->d_res.alloc(cap)) return ORBX_ERR_HIP;
     v->res_cap = cap;
   }
   if (v->nwords == 0) { /* if(empty()) return;  (:1133): empty vectors */
@@ -298,46 +275,38 @@ extern "C" int orbv_transform(orbv_vocab* v, const uint8_t* desc, int n, int lev
   if (!bow_word || !bow_value || !fv_node || !fv_feat) return ORBX_ERR_ARG;
   if (next_pow2(n) > ORBV_MAX_SORT) return ORBX_ERR_UNSUPPORTED;
   ORBX_TRY(hipSetDevice(v->device));
-  if (n > v->cap1) {
-    void* bufs[] = {v->d_desc1, v->d_cnt1, v->d_bw, v->d_fn, v->d_fo, v->d_ff, v->d_bv, v->d_n2};
-    for (void* b : bufs)
-      if (b) hipFree(b);
-    v->d_desc1 = nullptr; v->d_cnt1 = nullptr; v->d_bw = nullptr; v->d_fn = nullptr;
-    v->d_fo = nullptr; v->d_ff = nullptr; v->d_bv = nullptr; v->d_n2 = nullptr;
-    v->cap1 = 0;
+  orbv_vocab::Staging& g = v->one;
+  if (n > g.cap) {
+    g = orbv_vocab::Staging();
     const size_t c = (size_t)next_pow2(n);
-    if (hipMalloc((void**)&v->d_desc1, c * 32) != hipSuccess ||
-        hipMalloc((void**)&v->d_cnt1, sizeof(int)) != hipSuccess ||
-        hipMalloc((void**)&v->d_bw, c * 4) != hipSuccess ||
-        hipMalloc((void**)&v->d_fn, c * 4) != hipSuccess ||
-        hipMalloc((void**)&v->d_fo, (c + 1) * 4) != hipSuccess ||
-        hipMalloc((void**)&v->d_ff, c * 4) != hipSuccess ||
-        hipMalloc((void**)&v->d_bv, c * 8) != hipSuccess ||
-        hipMalloc((void**)&v->d_n2, 2 * sizeof(int)) != hipSuccess)
+    if (g.d_desc.alloc(c * 32) || g.d_cnt.alloc(1) || g.d_bw.alloc(c) || g.d_fn.alloc(c) ||
+        g.d_fo.alloc(c + 1) || g.d_ff.alloc(c) || g.d_bv.alloc(c) || g.d_n2.alloc(2)) {
+      g = orbv_vocab::Staging();
       return ORBX_ERR_HIP;
-    v->cap1 = (int)c;
+    }
+    g.cap = (int)c;
   }
   hipStream_t s = v->stream;
-  ORBX_TRY(hipMemcpyAsync(v->d_desc1, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
-  ORBX_TRY(hipMemcpyAsync(v->d_cnt1, &n, sizeof(int), hipMemcpyHostToDevice, s));
-  int rc = orbv_transform_batch(v, 1, v->d_desc1, v->d_cnt1, n, levelsup, v->d_bw, v->d_bv,
-                                v->d_n2, v->d_fn, v->d_fo, v->d_ff, v->d_n2 + 1, s);
+  ORBX_TRY(hipMemcpyAsync(g.d_desc, desc, (size_t)n * 32, hipMemcpyHostToDevice, s));
+  ORBX_TRY(hipMemcpyAsync(g.d_cnt, &n, sizeof(int), hipMemcpyHostToDevice, s));
+  int rc = orbv_transform_batch(v, 1, g.d_desc, g.d_cnt, n, levelsup, g.d_bw, g.d_bv,
+                                g.d_n2, g.d_fn, g.d_fo, g.d_ff, g.d_n2 + 1, s);
   if (rc) return rc;
   int cnts[2] = {0, 0};
-  ORBX_TRY(hipMemcpyAsync(cnts, v->d_n2, sizeof(cnts), hipMemcpyDeviceToHost, s));
+  ORBX_TRY(hipMemcpyAsync(cnts, g.d_n2, sizeof(cnts), hipMemcpyDeviceToHost, s));
   ORBX_TRY(hipStreamSynchronize(s));
   rc = orbv_check(v, s);
   if (rc) return rc;
   *nbow = cnts[0];
   *nfv = cnts[1];
-  ORBX_TRY(hipMemcpyAsync(bow_word, v->d_bw, (size_t)cnts[0] * 4, hipMemcpyDeviceToHost, s));
-  ORBX_TRY(hipMemcpyAsync(bow_value, v->d_bv, (size_t)cnts[0] * 8, hipMemcpyDeviceToHost, s));
-  ORBX_TRY(hipMemcpyAsync(fv_node, v->d_fn, (size_t)cnts[1] * 4, hipMemcpyDeviceToHost, s));
-  ORBX_TRY(hipMemcpyAsync(fv_off, v->d_fo, (size_t)(cnts[1] + 1) * 4, hipMemcpyDeviceToHost, s));
+  ORBX_TRY(hipMemcpyAsync(bow_word, g.d_bw, (size_t)cnts[0] * 4, hipMemcpyDeviceToHost, s));
+  ORBX_TRY(hipMemcpyAsync(bow_value, g.d_bv, (size_t)cnts[0] * 8, hipMemcpyDeviceToHost, s));
+  ORBX_TRY(hipMemcpyAsync(fv_node, g.d_fn, (size_t)cnts[1] * 4, hipMemcpyDeviceToHost, s));
+  ORBX_TRY(hipMemcpyAsync(fv_off, g.d_fo, (size_t)(cnts[1] + 1) * 4, hipMemcpyDeviceToHost, s));
   int nfeat = 0;
-  ORBX_TRY(hipMemcpyAsync(&nfeat, v->d_fo + cnts[1], 4, hipMemcpyDeviceToHost, s));
+  ORBX_TRY(hipMemcpyAsync(&nfeat, g.d_fo + cnts[1], 4, hipMemcpyDeviceToHost, s));
   ORBX_TRY(hipStreamSynchronize(s));
-  ORBX_TRY(hipMemcpyAsync(fv_feat, v->d_ff, (size_t)nfeat * 4, hipMemcpyDeviceToHost, s));
+  ORBX_TRY(hipMemcpyAsync(fv_feat, g.d_ff, (size_t)nfeat * 4, hipMemcpyDeviceToHost, s));
   ORBX_TRY(hipStreamSynchronize(s));
   return ORBX_OK;
 }

@@ -4,9 +4,11 @@
 
 #include <hip/hip_runtime.h>
 
+#include <utility>
 #include <vector>
 
 #include "../../include/orbx.h"
+#include "owned.h"
 
 #define ORBX_TRY(expr)                              \
   do {                                              \
@@ -33,24 +35,25 @@ namespace orbx {
 
 // HIP events recorded around every launch group of a stage, on the stream
 // the kernels run on.  collect() must be called after that stream is idle.
+// The timer owns its events: they go with the handle that holds it.
 struct StageTimer {
   bool enabled = false;
   struct Rec {
     int stage;
-    hipEvent_t a, b;
+    Event a, b;
   };
   std::vector<Rec> recs;
-  std::vector<hipEvent_t> pool;
-  hipEvent_t pending[ORBX_NSTAGES] = {};
+  std::vector<Event> pool;
+  Event pending[ORBX_NSTAGES];
 
-  hipEvent_t get() {
+  Event get() {
+    Event e;
     if (!pool.empty()) {
-      hipEvent_t e = pool.back();
+      e = std::move(pool.back());
       pool.pop_back();
-      return e;
+    } else {
+      e.create();
     }
-    hipEvent_t e = nullptr;
-    hipEventCreate(&e);
     return e;
   }
   void begin(int stage, hipStream_t s) {
@@ -60,15 +63,14 @@ struct StageTimer {
   }
   void end(int stage, hipStream_t s) {
     if (!enabled || !pending[stage]) return;
-    hipEvent_t b = get();
+    Event b = get();
     hipEventRecord(b, s);
-    recs.push_back({stage, pending[stage], b});
-    pending[stage] = nullptr;
+    recs.push_back({stage, std::move(pending[stage]), std::move(b)});
   }
   void reset(bool en) {
     for (auto& r : recs) {
-      pool.push_back(r.a);
-      pool.push_back(r.b);
+      pool.push_back(std::move(r.a));
+      pool.push_back(std::move(r.b));
     }
     recs.clear();
     enabled = en;
@@ -89,12 +91,19 @@ struct StageTimer {
     reset(enabled);
     return ORBX_OK;
   }
-  void release() {
-    reset(false);
-    for (auto e : pool) hipEventDestroy(e);
-    pool.clear();
-  }
 };
+
+// fills dst from v (room for at least one element): a blocking copy, or one
+// ordered on stream s, which v must outlive
+template <typename T>
+int upload(DevBuf<T>& dst, const std::vector<T>& v, bool blocking, hipStream_t s = nullptr) {
+  if (dst.alloc(v.size() ? v.size() : 1)) return ORBX_ERR_HIP;
+  if (v.empty()) return ORBX_OK;
+  const size_t bytes = v.size() * sizeof(T);
+  const hipError_t e = blocking ? hipMemcpy(dst, v.data(), bytes, hipMemcpyHostToDevice)
+                                : hipMemcpyAsync(dst, v.data(), bytes, hipMemcpyHostToDevice, s);
+  return e == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
+}
 
 // ---------------------------------------------------------------------------
 // Per-call workspaces of the synchronous drop-in entry points
@@ -111,6 +120,8 @@ struct StageTimer {
 // the slots out (inputs, outputs, scratch), sizes the buffers once, and does
 // the one upload (stage_in) and the one download (finish_call) below.
 // ---------------------------------------------------------------------------
+// Not owners (owned.h): a workspace lives as long as the process, and the
+// arena's host test points d and h at plain host memory.
 struct CallWs {
   int device = -1;
   hipStream_t stream = nullptr;
@@ -124,17 +135,6 @@ struct CallWs {
 
 CallWs* ws_acquire(int device);  // after hipSetDevice(device); nullptr on failure
 void ws_release(CallWs* w);
-
-// RAII lease of a pooled workspace
-struct WsLease {
-  CallWs* w;
-  explicit WsLease(int device) : w(ws_acquire(device)) {}
-  ~WsLease() {
-    if (w) ws_release(w);
-  }
-  WsLease(const WsLease&) = delete;
-  WsLease& operator=(const WsLease&) = delete;
-};
 
 // Completion wait of the synchronous drop-in calls: the caller (Tracking,
 // LoopClosing) blocks on the result anyway, so the stream is polled for up

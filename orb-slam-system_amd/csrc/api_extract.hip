@@ -8,11 +8,13 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <vector>
 
 #include "../../include/orbx.h"
 #include "api_common.h"
+#include "call_arena.h"
 #include "geometry.h"
 #include "plan_internal.h"
 
@@ -137,39 +139,6 @@ extern "C" int orbx_resize_tables(const orbx_params* p, int width, int height, i
 
 static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static void plan_free(orbx_plan* p) {
-  if (!p) return;
-  hipSetDevice(p->device);
-  void* bufs[] = {p->d_lv, p->d_cells, p->d_strips, p->d_xofs, p->d_xofs1, p->d_yofs, p->d_alpha, p->d_beta,
-                  p->d_pyr, p->d_blur, p->d_slots, p->d_ccount, p->d_qkeys, p->d_qout, p->d_qperm,
-                  p->d_qnode, p->d_lcount, p->d_err, p->d_fs_cnt, p->d_pyr_xs, p->d_pyr_ys, p->d_pyr_bo, p->d_pyr_blob};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  p->timer.release();
-  if (p->h_err) hipHostFree(p->h_err);
-  if (p->stream) hipStreamDestroy(p->stream);
-  if (p->s_aux) hipStreamDestroy(p->s_aux);
-  if (p->ev_aux0) hipEventDestroy(p->ev_aux0);
-  if (p->ev_aux1) hipEventDestroy(p->ev_aux1);
-  delete p;
-}
-
-// stream-ordered upload (the host vectors outlive the plan_create call,
-// which ends with a synchronisation of this stream only)
-template <typename T>
-static int upload(T** dst, const std::vector<T>& v, hipStream_t s) {
-  size_t n = v.size() ? v.size() : 1;
-  if (hipMalloc((void**)dst, n * sizeof(T)) != hipSuccess) return ORBX_ERR_HIP;
-  if (v.size() && hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s) != hipSuccess)
-    return ORBX_ERR_HIP;
-  return ORBX_OK;
-}
-
-static int dev_alloc(void** p, size_t bytes) {
-  if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return ORBX_ERR_HIP;
-  return ORBX_OK;
-}
-
 static std::atomic<int> g_debug_ccap{-1};
 
 extern "C" int orbx_debug_set_fast_ccap(int ccap) {
@@ -184,7 +153,8 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
   *out = nullptr;
   int ndev = orbx_device_count();
   if (device < 0 || device >= ndev) return ORBX_ERR_NO_DEVICE;
-  orbx_plan* p = new orbx_plan();
+  std::unique_ptr<orbx_plan> p(new orbx_plan());
+  p->device = device;
 #ifdef ORBX_PROFILING
   /* profiling builds only (tools/variant.sh): kernel phase early exits, grid
    * divisors, chunked passes; a release library never reads these (an
@@ -205,14 +175,13 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
     p->ccap_fixed_dbg = true;
   }
   int rc = plan_geometry(*prm, width, height, p->P);
-  if (rc) { delete p; return rc; }
+  if (rc) return rc;
   const Plan& P = p->P;
-  p->device = device;
   p->max_batch = max_batch;
   ORBX_TRY(hipSetDevice(device));
   // quadtree LDS: cell offsets + slot offsets, then (reusing them) 11 int arrays of qt_smax
   p->qt_lds = sizeof(int) * std::max(2 * (size_t)P.qt_max_cells + 1, 11 * (size_t)P.qt_smax);
-  if (p->qt_lds > 150 * 1024) { plan_free(p); return ORBX_ERR_UNSUPPORTED; }
+  if (p->qt_lds > 150 * 1024) return ORBX_ERR_UNSUPPORTED;
   // the wide single-frame form adds a second child array (4 smax ints)
   p->qt_lds_wide = sizeof(int) * std::max(2 * (size_t)P.qt_max_cells + 1, 15 * (size_t)P.qt_smax);
   if (set_max_dynamic_lds((const void*)k_quadtree, device) ||
@@ -220,15 +189,11 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
       set_max_dynamic_lds((const void*)k_quadtree_wide, device) ||
       set_max_dynamic_lds((const void*)k_fast_strips, device) ||
       set_max_dynamic_lds((const void*)k_fast_strips_p288, device) ||
-      set_max_dynamic_lds((const void*)k_pyramid, device)) { plan_free(p); return ORBX_ERR_HIP; }
-  if (p->overlap && (hipStreamCreateWithFlags(&p->s_aux, hipStreamNonBlocking) != hipSuccess ||
-                     hipEventCreateWithFlags(&p->ev_aux0, hipEventDisableTiming) != hipSuccess ||
-                     hipEventCreateWithFlags(&p->ev_aux1, hipEventDisableTiming) != hipSuccess)) {
-    plan_free(p);
+      set_max_dynamic_lds((const void*)k_pyramid, device)) return ORBX_ERR_HIP;
+  if (p->overlap && (p->s_aux.create() || p->ev_aux0.create(hipEventDisableTiming) ||
+                     p->ev_aux1.create(hipEventDisableTiming)))
     return ORBX_ERR_HIP;
-  }
-  if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&p->h_err, 64, hipHostMallocDefault) != hipSuccess) { plan_free(p); return ORBX_ERR_HIP; }
+  if (p->stream.create() || p->h_err.alloc(16)) return ORBX_ERR_HIP;
   memset(&p->bargs, 0, sizeof(p->bargs));
   // IC_Angle row extents (ORBextractor.cc:28-45): the centre row spans
   // [-15, 15], row v spans [-umax[|v|], umax[|v|]]
@@ -259,7 +224,7 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
     // (never used; the buffer range check does not cover the row offset):
     // they must be rows of the level.  Cells end at least 16 rows above the
     // level's last row, so this holds for every plan the geometry accepts
-    if (si.colwalk && si.y + si.h + FS_CW_RMAX > P.levels[si.level].h) { plan_free(p); return ORBX_ERR_UNSUPPORTED; }
+    if (si.colwalk && si.y + si.h + FS_CW_RMAX > P.levels[si.level].h) return ORBX_ERR_UNSUPPORTED;
     si.soff16 = si.level == 0 ? 0 : si.off + (long long)si.y * si.pitch + (si.x - si.lead16);
   }
   // plans with a pyramid run its waves and FAST's at a raised issue
@@ -381,54 +346,44 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
 #ifdef FS_LDS_PAD  // profiling variant: occupancy sensitivity of k_fast_strips
       G.lds += FS_LDS_PAD;
 #endif
-      if (G.lds > 150 * 1024) { plan_free(p); return ORBX_ERR_UNSUPPORTED; }
+      if (G.lds > 150 * 1024) return ORBX_ERR_UNSUPPORTED;
     }
   }
   hipStream_t us = p->stream;
-  if (upload(&p->d_lv, P.levels, us) || upload(&p->d_cells, P.cells, us) ||
-      upload(&p->d_strips, P.strips, us) || upload(&p->d_xofs, P.xofs, us) ||
-      upload(&p->d_xofs1, P.xofs1, us) || upload(&p->d_yofs, P.yofs, us) ||
-      upload(&p->d_alpha, P.alpha, us) || upload(&p->d_beta, P.beta, us) ||
-      upload(&p->d_pyr_xs, P.pyr_xs, us) || upload(&p->d_pyr_ys, P.pyr_ys, us) ||
-      upload(&p->d_pyr_bo, P.pyr_bo, us) || upload(&p->d_pyr_blob, P.pyr_kblob, us)) {
-    plan_free(p);
+  // stream-ordered uploads (the host vectors outlive this call, which ends
+  // with a synchronisation of this stream only)
+  if (upload(p->d_lv, P.levels, false, us) || upload(p->d_cells, P.cells, false, us) ||
+      upload(p->d_strips, P.strips, false, us) || upload(p->d_xofs, P.xofs, false, us) ||
+      upload(p->d_xofs1, P.xofs1, false, us) || upload(p->d_yofs, P.yofs, false, us) ||
+      upload(p->d_alpha, P.alpha, false, us) || upload(p->d_beta, P.beta, false, us) ||
+      upload(p->d_pyr_xs, P.pyr_xs, false, us) || upload(p->d_pyr_ys, P.pyr_ys, false, us) ||
+      upload(p->d_pyr_bo, P.pyr_bo, false, us) || upload(p->d_pyr_blob, P.pyr_kblob, false, us))
     return ORBX_ERR_HIP;
-  }
   p->pyr_stride = round_up((size_t)P.pyr_bytes, 256);
   p->blur_stride = round_up((size_t)P.blur_bytes, 256);
-  if (p->lb_auto && dev_alloc((void**)&p->d_blur, (size_t)max_batch * p->blur_stride)) {
-    plan_free(p);
-    return ORBX_ERR_HIP;
-  }
+  if (p->lb_auto && p->d_blur.alloc((size_t)max_batch * p->blur_stride)) return ORBX_ERR_HIP;
   p->slot_stride = round_up((size_t)P.nslots, 64);
   p->qk_stride = round_up((size_t)P.qk_elems, 64);
   p->qout_stride = round_up((size_t)P.kcap, 64);
   const size_t B = (size_t)max_batch;
-  if (dev_alloc((void**)&p->d_pyr, B * p->pyr_stride) ||
-      dev_alloc((void**)&p->d_slots, B * p->slot_stride * 4) ||
-      dev_alloc((void**)&p->d_ccount, B * (size_t)(P.ncells ? P.ncells : 1) * 4) ||
-      dev_alloc((void**)&p->d_qkeys, B * p->qk_stride * 4) ||
-      dev_alloc((void**)&p->d_qnode, B * p->qk_stride * 4) ||
-      dev_alloc((void**)&p->d_qout, B * p->qout_stride * 4) ||
-      dev_alloc((void**)&p->d_qperm, B * p->qout_stride * 4) ||
-      dev_alloc((void**)&p->d_lcount, B * (size_t)P.params.nlevels * 4) ||
-      dev_alloc((void**)&p->d_err, 16) ||
-      dev_alloc((void**)&p->d_fs_cnt, sizeof(int) * FS_CNT_LINES * FS_CNT_STRIDE)) {
-    plan_free(p);
+  if (p->d_pyr.alloc(B * p->pyr_stride) || p->d_slots.alloc(B * p->slot_stride) ||
+      p->d_ccount.alloc(B * (size_t)(P.ncells ? P.ncells : 1)) || p->d_qkeys.alloc(B * p->qk_stride) ||
+      p->d_qnode.alloc(B * p->qk_stride) || p->d_qout.alloc(B * p->qout_stride) ||
+      p->d_qperm.alloc(B * p->qout_stride) || p->d_lcount.alloc(B * (size_t)P.params.nlevels) ||
+      p->d_err.alloc(4) || p->d_fs_cnt.alloc(FS_CNT_LINES * FS_CNT_STRIDE))
     return ORBX_ERR_HIP;
-  }
   // stream-ordered: no device-wide synchronisation (other extractors and
   // the matcher may be running on this device from other threads)
   if (hipMemsetAsync(p->d_err, 0, 16, us) != hipSuccess ||
       hipMemsetAsync(p->d_fs_cnt, 0, sizeof(int) * FS_CNT_LINES * FS_CNT_STRIDE, us) != hipSuccess ||
       hipMemsetAsync(p->d_ccount, 0, B * (size_t)(P.ncells ? P.ncells : 1) * 4, us) != hipSuccess ||
-      hipStreamSynchronize(us) != hipSuccess) { plan_free(p); return ORBX_ERR_HIP; }
-  *out = p;
+      hipStreamSynchronize(us) != hipSuccess) return ORBX_ERR_HIP;
+  *out = p.release();
   return ORBX_OK;
 }
 
 extern "C" int orbx_plan_destroy(orbx_plan* p) {
-  plan_free(p);
+  delete p;
   return ORBX_OK;
 }
 
@@ -491,6 +446,8 @@ static int extract_pass(orbx_plan* p, const uint8_t* frames, int n, size_t fstri
   // row-streaming and fused kernels of round 4 measured slower and were
   // retired)
   p->timer.begin(ORBX_STAGE_RESIZE, s);
+  const int32_t *const pyr_xs = p->d_pyr_xs, *const pyr_ys = p->d_pyr_ys;
+  const uint32_t* const pyr_blob = p->d_pyr_blob;
   for (const PyrSeg& g : P.segs) {
     if (g.area) {
       hipLaunchKernelGGL(k_pyr_area2, dim3((unsigned)((g.w[1] + 1023) / 1024), (unsigned)g.h[1], (unsigned)n),
@@ -501,9 +458,9 @@ static int extract_pass(orbx_plan* p, const uint8_t* frames, int n, size_t fstri
     gp.prio = p->largs.prio;
     hipLaunchKernelGGL(k_pyramid, dim3(g.ntx * g.nty, n), dim3(256),
                        g.lds_a + g.lds_b + g.lds_yl + p->pad_pyr, s, frames, fstride, rstride,
-                       d_pyr, p->pyr_stride, gp, reinterpret_cast<const int4*>(p->d_pyr_xs),
-                       reinterpret_cast<const int4*>(p->d_pyr_ys),
-                       reinterpret_cast<const uint4*>(p->d_pyr_blob), p->d_pyr_bo, p->dbg);
+                       d_pyr, p->pyr_stride, gp, reinterpret_cast<const int4*>(pyr_xs),
+                       reinterpret_cast<const int4*>(pyr_ys), reinterpret_cast<const uint4*>(pyr_blob),
+                       p->d_pyr_bo, p->dbg);
   }
   p->timer.end(ORBX_STAGE_RESIZE, s);
   if (p->ev_after_pyr && hipEventRecord(p->ev_after_pyr, s) != hipSuccess) return ORBX_ERR_HIP;
@@ -626,7 +583,7 @@ extern "C" int orbx_plan_set_options(orbx_plan* p, int flags) {
   if ((flags & ORBX_PLAN_BRIEF_LEVEL) && !p->d_blur) {
     ORBX_TRY(hipSetDevice(p->device));
     ORBX_TRY(hipStreamSynchronize(p->stream));
-    if (dev_alloc((void**)&p->d_blur, (size_t)p->max_batch * p->blur_stride)) return ORBX_ERR_HIP;
+    if (p->d_blur.alloc((size_t)p->max_batch * p->blur_stride)) return ORBX_ERR_HIP;
   }
   p->options = flags;
   return ORBX_OK;
@@ -707,68 +664,39 @@ extern "C" int orbx_selftest_sincos_range(uint32_t first_bits, int n, float* sc,
   if (n == 0) return ORBX_OK;
   if (device < 0 || device >= orbx_device_count()) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
-  WsLease L(device);
-  CallWs* w = L.w;
-  if (!w) return ORBX_ERR_HIP;
-  const size_t bytes = (size_t)n * 8;
-  int rc = w->reserve(bytes, 0);
+  CallArena A(device);
+  if (!A.ok()) return ORBX_ERR_HIP;
+  const auto s_sc = A.out(sc, (size_t)n * 2);
+  const int rc = A.commit();
   if (rc) return rc;
-  hipLaunchKernelGGL(k_selftest_sincos_range, dim3((n + 255) / 256), dim3(256), 0, w->stream,
-                     first_bits, n, reinterpret_cast<float*>(w->d));
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  ORBX_TRY(hipMemcpyAsync(sc, w->d, bytes, hipMemcpyDeviceToHost, w->stream));
-  ORBX_TRY(hipStreamSynchronize(w->stream));
-  return ORBX_OK;
+  hipLaunchKernelGGL(k_selftest_sincos_range, dim3((n + 255) / 256), dim3(256), 0, A.stream(),
+                     first_bits, n, A.d(s_sc));
+  return A.finish();
 }
 
 // ---------------------------------------------------------------------------
 // orbx_extractor: the ORBextractor::operator() drop-in (host buffers).
 // ---------------------------------------------------------------------------
 
-static void extractor_release_plan(orbx_extractor* e) {
-  hipSetDevice(e->device);
-  orbx_stereo_release(e);
-  if (e->plan) orbx_plan_destroy(e->plan);
-  if (e->d_img) hipFree(e->d_img);
-  if (e->d_kps) hipFree(e->d_kps);
-  if (e->d_desc) hipFree(e->d_desc);
-  if (e->d_count) hipFree(e->d_count);
-  if (e->h_res) hipHostFree(e->h_res);
-  if (e->h_img) hipHostFree(e->h_img);
-  if (e->h_pyr) hipHostFree(e->h_pyr);
-  if (e->ev_pyr) hipEventDestroy(e->ev_pyr);
-  if (e->s_copy) hipStreamDestroy(e->s_copy);
-  e->plan = nullptr; e->d_img = nullptr; e->d_kps = nullptr; e->d_desc = nullptr;
-  e->d_count = nullptr; e->h_res = nullptr; e->d_res = nullptr; e->W = e->H = 0; e->have_frame = false;
-  e->h_img = nullptr; e->h_pyr = nullptr; e->ev_pyr = nullptr; e->s_copy = nullptr;
-  e->pyr_bytes = 0; e->host_pyr = false;
-}
-
 static int extractor_prepare(orbx_extractor* e, int W, int H) {
   if (e->plan && e->W == W && e->H == H) return ORBX_OK;
-  extractor_release_plan(e);
-  int rc = orbx_plan_create(&e->params, W, H, 1, e->device, &e->plan);
+  e->release_sized();
+  orbx_plan* plan = nullptr;
+  int rc = orbx_plan_create(&e->params, W, H, 1, e->device, &plan);
   if (rc) return rc;
-  const size_t kcap = (size_t)std::max(e->plan->P.kcap, 1);
-  if (dev_alloc((void**)&e->d_img, (size_t)W * H) ||
-      dev_alloc((void**)&e->d_kps, sizeof(orbx_keypoint) * kcap + 16) ||  /* + k_pack_results' last 16-B chunk */
-      dev_alloc((void**)&e->d_desc, 32 * kcap) ||
-      dev_alloc((void**)&e->d_count, sizeof(int)) ||
-      hipHostMalloc((void**)&e->h_res, 64 + 16 + (sizeof(orbx_keypoint) + 32) * kcap,
-                    hipHostMallocDefault) != hipSuccess ||
+  e->plan.reset(plan);
+  const size_t kcap = (size_t)std::max(plan->P.kcap, 1);
+  e->pyr_bytes = (size_t)plan->P.pyr_bytes;
+  if (e->d_img.alloc((size_t)W * H) ||
+      e->d_kps.alloc(kcap + 1) ||  /* + k_pack_results' last 16-B chunk */
+      e->d_desc.alloc(32 * kcap) || e->d_count.alloc(1) ||
+      e->h_res.alloc(64 + 16 + (sizeof(orbx_keypoint) + 32) * kcap) ||
       hipHostGetDevicePointer((void**)&e->d_res, e->h_res, 0) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_img, (size_t)W * H, hipHostMallocDefault) != hipSuccess) {
-    extractor_release_plan(e);
+      e->h_img.alloc((size_t)W * H) || (e->pyr_bytes && e->h_pyr.alloc(e->pyr_bytes)) ||
+      e->s_copy.create() || e->ev_pyr.create(hipEventDisableTiming)) {
+    e->release_sized();
     return ORBX_ERR_HIP;
   }
-  e->pyr_bytes = (size_t)e->plan->P.pyr_bytes;
-  if ((e->pyr_bytes && hipHostMalloc((void**)&e->h_pyr, e->pyr_bytes, hipHostMallocDefault) != hipSuccess) ||
-      hipStreamCreateWithFlags(&e->s_copy, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->ev_pyr, hipEventDisableTiming) != hipSuccess) {
-    extractor_release_plan(e);
-    return ORBX_ERR_HIP;
-  }
-  e->last_k = 0;
   e->W = W;
   e->H = H;
   return ORBX_OK;
@@ -789,8 +717,6 @@ extern "C" int orbx_extractor_create(const orbx_params* p, int device, orbx_extr
 }
 
 extern "C" int orbx_extractor_destroy(orbx_extractor* e) {
-  if (!e) return ORBX_OK;
-  extractor_release_plan(e);
   delete e;
   return ORBX_OK;
 }
@@ -817,7 +743,7 @@ extern "C" int orbx_extract(orbx_extractor* e, const uint8_t* img, int W, int H,
   int rc = extractor_prepare(e, W, H);
   if (rc) return rc;
   ORBX_TRY(hipSetDevice(e->device));
-  orbx_plan* p = e->plan;
+  orbx_plan* p = e->plan.get();
   hipStream_t s = p->stream;
   e->host_pyr = false;
   ++e->n_calls;
@@ -847,18 +773,21 @@ extern "C" int orbx_extract(orbx_extractor* e, const uint8_t* img, int W, int H,
   // one launch writes the count, the error word and exactly the frame's
   // rows into the pinned staging (k_pack_results, over PCIe)
   const int kcap = std::max(p->P.kcap, 1);
-  const int* h_hdr = reinterpret_cast<const int*>(e->h_res);  // {count, error word}
-  orbx_keypoint* h_kps = reinterpret_cast<orbx_keypoint*>(e->h_res + 64);
+  uint8_t* const h_res = e->h_res;
+  const int* h_hdr = reinterpret_cast<const int*>(h_res);  // {count, error word}
+  orbx_keypoint* h_kps = reinterpret_cast<orbx_keypoint*>(h_res + 64);
   // descriptor rows at a 16-B boundary (k_pack_results copies 16 B per lane)
   const size_t desc_off = (64 + sizeof(orbx_keypoint) * (size_t)kcap + 15) & ~(size_t)15;
-  uint8_t* h_desc = e->h_res + desc_off;
+  uint8_t* h_desc = h_res + desc_off;
+  orbx_keypoint* const d_kps = e->d_kps;
+  uint8_t* const d_desc = e->d_desc;
   auto chain = [&]() -> int {
-    const int r = orbx_plan_extract(p, e->d_img, 1, (size_t)W * H, (size_t)W, e->d_kps, e->d_desc,
+    const int r = orbx_plan_extract(p, e->d_img, 1, (size_t)W * H, (size_t)W, d_kps, d_desc,
                                     e->d_count, s);
     if (r) return r;
     hipLaunchKernelGGL(k_pack_results, dim3(std::min((kcap * 8 + 255) / 256, 64)), dim3(256), 0, s,
-                       p->d_err, e->d_count, reinterpret_cast<const uint4*>(e->d_kps),
-                       reinterpret_cast<const uint4*>(e->d_desc), kcap, reinterpret_cast<uint4*>(e->d_res),
+                       p->d_err, e->d_count, reinterpret_cast<const uint4*>(d_kps),
+                       reinterpret_cast<const uint4*>(d_desc), kcap, reinterpret_cast<uint4*>(e->d_res),
                        (uint32_t)(desc_off / 16));
     return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
   };
@@ -866,7 +795,7 @@ extern "C" int orbx_extract(orbx_extractor* e, const uint8_t* img, int W, int H,
   // change in the call's latency, p50 174-176 us either way in the probe --
   // the gap after the upload is the pageable copy's completion, not the
   // host's launches; not kept)
-  p->ev_after_pyr = to_host ? e->ev_pyr : nullptr;
+  p->ev_after_pyr = to_host ? (hipEvent_t)e->ev_pyr : nullptr;
   rc = chain();
   p->ev_after_pyr = nullptr;
   if (rc) return rc;

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "../../include/orbx.h"
@@ -396,23 +397,25 @@ struct orbm_plan {
    * default: any other descriptor source gets all 8 dwords. */
   bool six_words = false;
   bool force_valu = false; /* ORBM_PLAN_VALU: popcount kernel instead of the MFMA path */
-  MProblem* d_probs = nullptr;
-  MNodePair* d_nps = nullptr;
-  uint32_t* d_sel = nullptr;
-  MatchScratch sc; /* gval2 stays null: no validity masks */
+  DevBuf<MProblem> d_probs;
+  DevBuf<MNodePair> d_nps;
+  DevBuf<uint32_t> d_sel;
+  /* launch_match's scratch (MatchScratch) */
+  DevBuf<uint4> d_gdesc2;
+  DevBuf<uint8_t> d_gx2;
+  DevBuf<uint2> d_cand;
+  DevBuf<int4> d_rowinfo;
+  DevBuf<int2> d_ev;
+  DevBuf<int> d_last, d_last_off;
   StageTimer timer;
-};
+  ~orbm_plan() { hipSetDevice(device); }
 
-static void mplan_free(orbm_plan* m) {
-  if (!m) return;
-  hipSetDevice(m->device);
-  void* b[] = {m->d_probs, m->d_nps, m->d_sel, m->sc.cand, m->sc.gdesc2, m->sc.gx2, m->sc.rowinfo,
-               m->sc.ev, m->sc.last, m->sc.last_off};
-  for (void* p : b)
-    if (p) hipFree(p);
-  m->timer.release();
-  delete m;
-}
+  /* no validity masks (gval2); the +-1 bytes unless the popcount path is forced */
+  MatchScratch scratch() const {
+    uint8_t* const gx2 = force_valu ? nullptr : d_gx2;
+    return MatchScratch{d_gdesc2, nullptr, gx2, d_cand, d_rowinfo, d_ev, d_last, d_last_off};
+  }
+};
 
 extern "C" int orbm_plan_create(int max_pairs, int kcap, int topn, int device, orbm_plan** out) {
   if (!out || max_pairs < 1 || kcap < 1 || topn < 1 || topn > 0xFFFF || kcap > ORBM_MAX_N2)
@@ -420,31 +423,23 @@ extern "C" int orbm_plan_create(int max_pairs, int kcap, int topn, int device, o
   *out = nullptr;
   if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
-  orbm_plan* m = new orbm_plan();
+  std::unique_ptr<orbm_plan> m(new orbm_plan());
   m->device = device;
   m->max_pairs = max_pairs;
   m->kcap = kcap;
   m->topn = topn;
   const size_t P = (size_t)max_pairs, rows = P * topn;
-  if (hipMalloc((void**)&m->d_probs, P * sizeof(MProblem)) != hipSuccess ||
-      hipMalloc((void**)&m->d_nps, P * sizeof(MNodePair)) != hipSuccess ||
-      hipMalloc((void**)&m->d_sel, P * 2 * topn * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&m->sc.cand, rows * ORBM_T * sizeof(uint2)) != hipSuccess ||
-      hipMalloc((void**)&m->sc.gdesc2, rows * 2 * sizeof(uint4)) != hipSuccess ||
-      hipMalloc(&m->sc.gx2, rows * 256) != hipSuccess ||
-      hipMalloc((void**)&m->sc.rowinfo, rows * sizeof(int4)) != hipSuccess ||
-      hipMalloc((void**)&m->sc.ev, rows * sizeof(int2)) != hipSuccess ||
-      hipMalloc((void**)&m->sc.last, P * kcap * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&m->sc.last_off, P * sizeof(int)) != hipSuccess) {
-    mplan_free(m);
+  if (m->d_probs.alloc(P) || m->d_nps.alloc(P) || m->d_sel.alloc(P * 2 * topn) ||
+      m->d_cand.alloc(rows * ORBM_T) || m->d_gdesc2.alloc(rows * 2) || m->d_gx2.alloc(rows * 256) ||
+      m->d_rowinfo.alloc(rows) || m->d_ev.alloc(rows) || m->d_last.alloc(P * kcap) ||
+      m->d_last_off.alloc(P))
     return ORBX_ERR_HIP;
-  }
-  *out = m;
+  *out = m.release();
   return ORBX_OK;
 }
 
 extern "C" int orbm_plan_destroy(orbm_plan* m) {
-  mplan_free(m);
+  delete m;
   return ORBX_OK;
 }
 
@@ -481,13 +476,11 @@ extern "C" int orbm_plan_match_frames(orbm_plan* m, int npairs, const orbx_keypo
   m->timer.begin(ORBX_STAGE_MSELECT, s);
   hipLaunchKernelGGL(k_match_setup, dim3((npairs + 63) / 64), dim3(64), 0, s, m->d_probs,
                      m->d_nps, npairs, kps_a, desc_a, kps_b, desc_b, m->kcap, m->topn, m->d_sel,
-                     match12, nmatches, nnratio, check_ori ? 1 : 0, m->sc.last_off);
+                     match12, nmatches, nnratio, check_ori ? 1 : 0, m->d_last_off);
   hipLaunchKernelGGL(k_match_select, dim3(npairs, 2), dim3(256), 0, s, m->d_probs, m->d_nps,
                      kps_a, count_a, kps_b, count_b, m->kcap, m->topn, m->d_sel);
   m->timer.end(ORBX_STAGE_MSELECT, s);
   const MatchShape sh = {npairs, npairs, npairs * m->topn, 0, m->topn, m->topn, m->kcap, m->six_words};
-  MatchScratch sc = m->sc;
-  if (m->force_valu) sc.gx2 = nullptr;
-  launch_match(m->d_probs, m->d_nps, sh, sc, s, &m->timer);
+  launch_match(m->d_probs, m->d_nps, sh, m->scratch(), s, &m->timer);
   return hipGetLastError() == hipSuccess ? ORBX_OK : ORBX_ERR_HIP;
 }

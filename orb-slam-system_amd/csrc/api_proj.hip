@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
 
 #include "../../include/orbx.h"
 #include "call_arena.h"
@@ -99,27 +100,15 @@ extern "C" int orbm_search_by_projection(int mode, const orbx_proj_frame* F,
 // ---------------------------------------------------------------------------
 struct orbm_proj_plan {
   int device = 0, max_prob = 0, max_n = 0, max_nq = 0;
-  ProjProblem* d_probs = nullptr;
-  ProjProblem* h_probs = nullptr;  // pinned staging of the problem table
-  hipEvent_t ev = nullptr;         // the last table upload (h_probs reusable after it)
-  hipEvent_t ev_done = nullptr;    // the last call's kernels (its grid / candidate scratch free after it)
-  int* d_cell_off = nullptr;
-  int* d_cell_feat = nullptr;
-  uint32_t* d_cand = nullptr;
-  int* d_ncand = nullptr;
+  DevBuf<ProjProblem> d_probs;
+  PinnedBuf<ProjProblem> h_probs;  // pinned staging of the problem table
+  Event ev;                        // the last table upload (h_probs reusable after it)
+  Event ev_done;                   // the last call's kernels (its grid / candidate scratch free after it)
+  DevBuf<int> d_cell_off, d_cell_feat;
+  DevBuf<uint32_t> d_cand;
+  DevBuf<int> d_ncand;
+  ~orbm_proj_plan() { hipSetDevice(device); }
 };
-
-static void proj_plan_free(orbm_proj_plan* p) {
-  if (!p) return;
-  hipSetDevice(p->device);
-  if (p->ev) hipEventDestroy(p->ev);
-  if (p->ev_done) hipEventDestroy(p->ev_done);
-  if (p->h_probs) hipHostFree(p->h_probs);
-  void* bufs[] = {p->d_probs, p->d_cell_off, p->d_cell_feat, p->d_cand, p->d_ncand};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  delete p;
-}
 
 extern "C" int orbm_proj_plan_create(int max_problems, int max_n, int max_nq, int device, orbm_proj_plan** out) {
   if (!out || max_problems < 1 || max_n < 1 || max_nq < 0) return ORBX_ERR_ARG;
@@ -127,34 +116,25 @@ extern "C" int orbm_proj_plan_create(int max_problems, int max_n, int max_nq, in
   if (max_n > PJ_MAXN || max_problems > 65535) return ORBX_ERR_UNSUPPORTED;
   if (check_device(device)) return ORBX_ERR_NO_DEVICE;
   ORBX_TRY(hipSetDevice(device));
-  orbm_proj_plan* p = new orbm_proj_plan();
+  std::unique_ptr<orbm_proj_plan> p(new orbm_proj_plan());
   p->device = device;
   p->max_prob = max_problems;
   p->max_n = max_n;
   p->max_nq = max_nq;
   const size_t B = (size_t)max_problems;
-  if (hipMalloc((void**)&p->d_probs, B * sizeof(ProjProblem)) != hipSuccess ||
-      hipHostMalloc((void**)&p->h_probs, B * sizeof(ProjProblem), hipHostMallocDefault) != hipSuccess ||
-      hipEventCreateWithFlags(&p->ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&p->ev_done, hipEventDisableTiming) != hipSuccess ||
-      hipMalloc((void**)&p->d_cell_off, B * (PG_CELLS + 1) * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&p->d_cell_feat, B * (size_t)max_n * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&p->d_cand, B * (size_t)std::max(max_nq, 1) * PJ_T * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void**)&p->d_ncand, B * (size_t)std::max(max_nq, 1) * sizeof(int)) != hipSuccess) {
-    proj_plan_free(p);
+  const size_t Q = B * (size_t)std::max(max_nq, 1);
+  if (p->d_probs.alloc(B) || p->h_probs.alloc(B) || p->ev.create(hipEventDisableTiming) ||
+      p->ev_done.create(hipEventDisableTiming) || p->d_cell_off.alloc(B * (PG_CELLS + 1)) ||
+      p->d_cell_feat.alloc(B * (size_t)max_n) || p->d_cand.alloc(Q * PJ_T) || p->d_ncand.alloc(Q) ||
+      set_max_dynamic_lds((const void*)k_grid_build, device) ||
+      set_max_dynamic_lds((const void*)k_proj_resolve, device))
     return ORBX_ERR_HIP;
-  }
-  if (set_max_dynamic_lds((const void*)k_grid_build, device) ||
-      set_max_dynamic_lds((const void*)k_proj_resolve, device)) {
-    proj_plan_free(p);
-    return ORBX_ERR_HIP;
-  }
-  *out = p;
+  *out = p.release();
   return ORBX_OK;
 }
 
 extern "C" int orbm_proj_plan_destroy(orbm_proj_plan* p) {
-  proj_plan_free(p);
+  delete p;
   return ORBX_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 
 #include "../../include/orbx.h"
 #include "api_common.h"
@@ -25,44 +26,11 @@ __global__ void k_stereo_filter(const int*, const StereoArgs, float*, float*, co
 
 using namespace orbx;
 
-struct orbs_plan {
-  int device = 0, max_batch = 0, waves = 4;
-  int sm_div = 0; /* ORBX_DEBUG_SMDIV: k_stereo_match keypoints per wave, profiling only */
-  orbx_params params;
-  int W = 0, H = 0;
-  StereoArgs args;
-  int* d_rowoff = nullptr;
-  uint2* d_rows = nullptr; /* CSR entries {iR | octave << 16, x} (kernels_stereo.hip) */
-  int* d_sad = nullptr;
-  int* d_err = nullptr;
-  /* host drop-in (orbx_stereo_match) staging, batch 1 */
-  orbx_keypoint *d_kl = nullptr, *d_kr = nullptr;
-  uint8_t *d_dl = nullptr, *d_dr = nullptr;
-  int* d_cnt = nullptr; /* [2]: left, right */
-  float *d_ur = nullptr, *d_dep = nullptr;
-  int* d_nm = nullptr;
-  hipStream_t stream = nullptr;
-  StageTimer timer;
-};
-
-static void splan_free(orbs_plan* sp) {
-  if (!sp) return;
-  hipSetDevice(sp->device);
-  void* bufs[] = {sp->d_rowoff, sp->d_rows, sp->d_sad, sp->d_err, sp->d_kl, sp->d_kr,
-                  sp->d_dl,     sp->d_dr,   sp->d_cnt, sp->d_ur,  sp->d_dep, sp->d_nm};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  sp->timer.release();
-  if (sp->stream) hipStreamDestroy(sp->stream);
-  delete sp;
-}
-
-static int splan_create(const orbx_plan* g, int max_batch, orbs_plan** out) {
-  *out = nullptr;
+static int splan_create(const orbx_plan* g, int max_batch, std::unique_ptr<orbs_plan>& out) {
   const Plan& P = g->P;
   const int L = P.params.nlevels;
   if (P.H > ORBX_STEREO_MAXROWS || P.kcap > 65535 || L > ORBX_MAX_LEVELS) return ORBX_ERR_UNSUPPORTED;
-  orbs_plan* sp = new orbs_plan();
+  std::unique_ptr<orbs_plan> sp(new orbs_plan());
   sp->device = g->device;
   sp->max_batch = max_batch;
   sp->params = P.params;
@@ -95,32 +63,27 @@ static int splan_create(const orbx_plan* g, int max_batch, orbs_plan** out) {
   hipSetDevice(sp->device);
   const size_t B = (size_t)max_batch;
   const size_t K = (size_t)std::max(P.kcap, 1);
-  if (hipMalloc((void**)&sp->d_rowoff, B * (A.nrows + 1) * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&sp->d_rows, B * (size_t)std::max(A.rcap, 1) * sizeof(uint2)) != hipSuccess ||
-      hipMalloc((void**)&sp->d_sad, B * K * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&sp->d_err, 16) != hipSuccess ||
-      hipMemset(sp->d_err, 0, 16) != hipSuccess ||
-      hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking) != hipSuccess) {
-    splan_free(sp);
+  /* k_stereo_rows' dynamic LDS, nrows ints, stays within the default limit:
+   * nrows <= ORBX_STEREO_MAXROWS */
+  if (sp->d_rowoff.alloc(B * (A.nrows + 1)) || sp->d_rows.alloc(B * (size_t)std::max(A.rcap, 1)) ||
+      sp->d_sad.alloc(B * K) || sp->d_err.alloc(4) || hipMemset(sp->d_err, 0, 16) != hipSuccess ||
+      sp->stream.create())
     return ORBX_ERR_HIP;
-  }
-  if (A.nrows * sizeof(int) > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)k_stereo_rows, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)(A.nrows * sizeof(int))) != hipSuccess) {
-    splan_free(sp);
-    return ORBX_ERR_HIP;
-  }
-  *out = sp;
+  out = std::move(sp);
   return ORBX_OK;
 }
 
 extern "C" int orbs_plan_create(const orbx_plan* geometry, int max_batch, orbs_plan** out) {
   if (!geometry || !out || max_batch < 1) return ORBX_ERR_ARG;
-  return splan_create(geometry, max_batch, out);
+  *out = nullptr;
+  std::unique_ptr<orbs_plan> sp;
+  const int rc = splan_create(geometry, max_batch, sp);
+  *out = sp.release();
+  return rc;
 }
 
 extern "C" int orbs_plan_destroy(orbs_plan* sp) {
-  splan_free(sp);
+  delete sp;
   return ORBX_OK;
 }
 
@@ -232,29 +195,20 @@ extern "C" int orbx_stereo_match(orbx_extractor* left, orbx_extractor* right,
     return ORBX_ERR_ARG;
   if (nmatches) *nmatches = 0;
   if (nl == 0) return ORBX_OK;
-  orbs_plan* sp = reinterpret_cast<orbs_plan*>(left->stereo);
-  if (sp && !same_geometry(sp, left->plan)) {
-    splan_free(sp);
-    left->stereo = sp = nullptr;
-  }
-  if (!same_geometry_pair(left->plan, right->plan)) return ORBX_ERR_ARG;
-  if (!sp) {
-    int rc = splan_create(left->plan, 1, &sp);
+  const orbx_plan* const lp = left->plan.get();
+  if (left->stereo && !same_geometry(left->stereo.get(), lp)) left->stereo.reset();
+  if (!same_geometry_pair(lp, right->plan.get())) return ORBX_ERR_ARG;
+  if (!left->stereo) {
+    std::unique_ptr<orbs_plan> made;
+    int rc = splan_create(lp, 1, made);
     if (rc) return rc;
-    const size_t K = (size_t)std::max(left->plan->P.kcap, 1);
-    if (hipMalloc((void**)&sp->d_kl, K * sizeof(orbx_keypoint)) != hipSuccess ||
-        hipMalloc((void**)&sp->d_kr, K * sizeof(orbx_keypoint)) != hipSuccess ||
-        hipMalloc((void**)&sp->d_dl, K * 32) != hipSuccess ||
-        hipMalloc((void**)&sp->d_dr, K * 32) != hipSuccess ||
-        hipMalloc((void**)&sp->d_cnt, 2 * sizeof(int)) != hipSuccess ||
-        hipMalloc((void**)&sp->d_ur, K * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&sp->d_dep, K * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&sp->d_nm, sizeof(int)) != hipSuccess) {
-      splan_free(sp);
+    const size_t K = (size_t)std::max(lp->P.kcap, 1);
+    if (made->d_kl.alloc(K) || made->d_kr.alloc(K) || made->d_dl.alloc(K * 32) || made->d_dr.alloc(K * 32) ||
+        made->d_cnt.alloc(2) || made->d_ur.alloc(K) || made->d_dep.alloc(K) || made->d_nm.alloc(1))
       return ORBX_ERR_HIP;
-    }
-    left->stereo = sp;
+    left->stereo = std::move(made);
   }
+  orbs_plan* const sp = left->stereo.get();
   if (nl > sp->args.kcap || nr > sp->args.kcap) return ORBX_ERR_CAPACITY;
   ORBX_TRY(hipSetDevice(sp->device));
   hipStream_t s = sp->stream;
@@ -281,11 +235,4 @@ extern "C" int orbx_stereo_match(orbx_extractor* left, orbx_extractor* right,
   if (rc) return rc;
   if (nmatches) *nmatches = nm;
   return ORBX_OK;
-}
-
-void orbx_stereo_release(orbx_extractor* e) {
-  if (e && e->stereo) {
-    splan_free(reinterpret_cast<orbs_plan*>(e->stereo));
-    e->stereo = nullptr;
-  }
 }

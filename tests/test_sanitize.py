@@ -4,7 +4,8 @@ with -fsanitize=address,undefined on the host side only (-Xarch_host; no GPU
 sanitizer), links tests/cpp/sanitize_main.cpp, and runs it on the CPU:
 geometry planning over a size/parameter sweep plus malformed-argument calls
 of every entry point; and tests/cpp/arena_main.cpp, the drop-in calls' typed
-arena (csrc/call_arena.h) over two host buffers.  Leak checking is off (the HIP runtime keeps its
+arena (csrc/call_arena.h) over two host buffers; and tests/cpp/owned_main.cpp,
+the handles' resource owners (csrc/owned.h) over malloc'd blocks.  Leak checking is off (the HIP runtime keeps its
 allocations until exit)."""
 import os
 import subprocess
@@ -26,3 +27,8 @@ def test_host_code_clean_under_asan_ubsan():
     assert a.returncode == 0, a.stdout + a.stderr
     assert "0 failures" in a.stdout
     assert "runtime error" not in a.stderr and "AddressSanitizer" not in a.stderr
+    o = subprocess.run([os.path.join(PKG, "build_asan", "owned_main")], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert o.returncode == 0, o.stdout + o.stderr
+    assert "0 failures" in o.stdout
+    assert "runtime error" not in o.stderr and "AddressSanitizer" not in o.stderr
