@@ -3,6 +3,9 @@
  * Drop-in boundary for the reference's hot path:
  *   ORB_SLAM2::ORBextractor   /root/reference/include/ORBextractor.h:25-91
  *   ORB_SLAM2::ORBmatcher     /root/reference/include/ORBmatcher.h:16-81
+ *   ORBVocabulary::score and ORB_SLAM2::KeyFrameDatabase's word walk
+ *                             include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc
+ *                             (orbv_score, orbv_db_*: place recognition)
  * Plain C: POD structs, raw pointers, explicit sizes, int status codes, no
  * exceptions across the boundary, no torch types.  Every compute entry point
  * runs hand-written HIP kernels on a gfx950 device; there is no CPU path.
@@ -28,8 +31,9 @@ extern "C" {
  * orbm_search_for_triangulation, and orbx_kf_frame / orbx_kf_query and
  * orbm_keyframe_search, and orbx_init_pair and
  * orbm_search_for_initialization, and the debug entry points
- * orbx_debug_live_resources / orbx_debug_fail_acquire, are additive (no
- * existing struct or entry point changes), so the version stays 2. */
+ * orbx_debug_live_resources / orbx_debug_fail_acquire, and orbv_score and the
+ * orbv_db_* keyframe database, are additive (no existing struct or entry
+ * point changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
 /* status codes */
@@ -564,6 +568,46 @@ int orbv_transform_batch(orbv_vocab* v, int nframes, const uint8_t* d_desc, cons
                          int* d_nbow, uint32_t* d_fv_node, uint32_t* d_fv_off, uint32_t* d_fv_feat,
                          int* d_nfv, void* stream);
 int orbv_check(orbv_vocab* v, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Place recognition: the two consumers of the BowVector.
+ *   TemplatedVocabulary::score(a, b)     TemplatedVocabulary.h:1199-1203,
+ *                                        Thirdparty/DBoW2/DBoW2/ScoringObject.cpp
+ *   KeyFrameDatabase add / erase / clear and the word walk of
+ *   DetectLoopCandidates / DetectRelocalizationCandidates
+ *                                        src/KeyFrameDatabase.cc:56-85,179-203
+ * BowVectors in the layout orbv_transform emits: word[n] strictly ascending
+ * and below the vocabulary's nwords (else ORBX_ERR_ARG), value[n] finite
+ * doubles (not necessarily normalised); more than 8192 words in one vector:
+ * ORBX_ERR_UNSUPPORTED.  Scores are bit-equal to ScoringObject.cpp for the
+ * vocabulary's scoring L1_NORM (0), L2_NORM (1), CHI_SQUARE (2) and
+ * DOT_PRODUCT (5); KL (3) and BHATTACHARYYA (4): ORBX_ERR_UNSUPPORTED.
+ * ------------------------------------------------------------------------- */
+/* TemplatedVocabulary::score of one vector against nvec vectors (CSR: vector j is
+ * b_word/b_value[b_off[j] .. b_off[j+1])), with the vocabulary's scoring. Host buffers,
+ * synchronous. */
+int orbv_score(const orbv_vocab* v, const uint32_t* a_word, const double* a_value, int na,
+               const uint32_t* b_off, const uint32_t* b_word, const double* b_value, int nvec,
+               double* score);
+
+/* The keyframe database: the stored BowVectors live on the device.  The
+ * vocabulary is read at creation only (scoring, nwords).  One host thread
+ * calls a given orbv_db at a time (the reference holds mMutex). */
+typedef struct orbv_db orbv_db;
+/* reserve_words: initial capacity of the device word store (0 = default); it grows on demand */
+int orbv_db_create(const orbv_vocab* v, size_t reserve_words, int device, orbv_db** out);
+int orbv_db_destroy(orbv_db* db);
+/* ORBX_ERR_ARG for a kf_id already present */
+int orbv_db_add(orbv_db* db, uint64_t kf_id, const uint32_t* word, const double* value, int n);
+int orbv_db_erase(orbv_db* db, uint64_t kf_id);   /* an absent id is a no-op, as in the reference */
+int orbv_db_clear(orbv_db* db);
+int orbv_db_size(const orbv_db* db, int* nkf);
+/* Every stored keyframe that shares at least one word with the query, in the order the reference's
+ * lKFsSharingWords would hold them if nothing were excluded; per entry its id, the number of
+ * common words, and score(query, keyframe). cap entries; ORBX_ERR_CAPACITY with *nsharing = the
+ * required count.  n == 0 or an empty database: ORBX_OK with *nsharing = 0. */
+int orbv_db_query(orbv_db* db, const uint32_t* word, const double* value, int n, int cap,
+                  uint64_t* kf_id, int32_t* ncommon, double* score, int* nsharing);
 
 /* ---------------------------------------------------------------------------
  * Projection matchers: the frame grid

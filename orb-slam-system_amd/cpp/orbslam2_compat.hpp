@@ -32,8 +32,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <list>
 #include <map>
 #include <memory>
+#include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -910,7 +913,12 @@ class ORBmatcher {
 //     ORB_SLAM2::ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor,
 //     FORB>, include/ORBVocabulary.h) with loadFromTextFile / empty /
 //     transform(features, BowVector&, FeatureVector&, levelsup), as
-//     Frame::ComputeBoW (src/Frame.cc:373-382) and System's loader call them;
+//     Frame::ComputeBoW (src/Frame.cc:373-382) and System's loader call them,
+//     and size() / score(a, b) as KeyFrameDatabase and LoopClosing::DetectLoop
+//     call them (plus a batched score for DetectLoop's whole loop);
+//   * ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h) as a template
+//     over the caller's KeyFrame and Frame: add / erase / clear,
+//     DetectLoopCandidates, DetectRelocalizationCandidates;
 //   * Frame::ComputeStereoMatches (src/Frame.cc:446-620) as a template over
 //     the caller's Frame, reading and writing exactly the members the
 //     reference's member function does.
@@ -968,8 +976,267 @@ class ORBVocabulary {
                                                                               feat.begin() + off[j + 1])));
   }
 
+  // TemplatedVocabulary::size() (:1001-1004): the number of words;
+  // KeyFrameDatabase's constructor sizes its inverted file by it
+  unsigned int size() const {
+    int nwords = 0;
+    if (!v_ || orbv_vocab_info(v_, nullptr, nullptr, nullptr, nullptr, nullptr, &nwords)) return 0;
+    return (unsigned int)nwords;
+  }
+  // TemplatedVocabulary::score(a, b) (:1199-1203) with the vocabulary's scoring
+  double score(const DBoW2::BowVector& a, const DBoW2::BowVector& b) const {
+    std::vector<const DBoW2::BowVector*> one(1, &b);
+    std::vector<double> s;
+    score(a, one, s);
+    return s[0];
+  }
+  // the same for many b in one call (LoopClosing::DetectLoop's minScore loop,
+  // src/LoopClosing.cc:67-74): scores[j] = score(a, *b[j])
+  void score(const DBoW2::BowVector& a, const std::vector<const DBoW2::BowVector*>& b,
+             std::vector<double>& scores) const {
+    std::vector<uint32_t> aw, bw, off(1, 0u);
+    std::vector<double> av, bv;
+    Flatten(a, aw, av);
+    for (const DBoW2::BowVector* p : b) {
+      Flatten(*p, bw, bv);
+      off.push_back((uint32_t)bw.size());
+    }
+    scores.assign(b.size(), 0.0);
+    orbx_throw(orbv_score(v_, aw.data(), av.data(), (int)aw.size(), off.data(), bw.data(), bv.data(), (int)b.size(),
+                          scores.data()),
+               "ORBVocabulary::score");
+  }
+
+  // appends a BowVector (a std::map: ascending words) to the C ABI's layout
+  static void Flatten(const DBoW2::BowVector& v, std::vector<uint32_t>& word, std::vector<double>& value) {
+    for (DBoW2::BowVector::const_iterator it = v.begin(); it != v.end(); ++it) {
+      word.push_back(it->first);
+      value.push_back(it->second);
+    }
+  }
+  const orbv_vocab* Orbv() const { return v_; }
+
  private:
   orbv_vocab* v_ = nullptr;
+};
+
+// KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc) as a
+// template over the caller's KeyFrame and Frame classes.  The inverted file
+// is the device store behind orbv_db: add / erase / clear keep it, and one
+// orbv_db_query per Detect*Candidates call returns what the reference's walk
+// over mvInvertedFile collects -- every keyframe sharing a word, in
+// lKFsSharingWords' order, with its number of common words and its score.
+// Everything after the walk needs the caller's graph and runs here on that
+// list as the reference words it, reading and writing exactly the members the
+// reference does: KF::mnId, mBowVec, mnLoopQuery, mnLoopWords, mLoopScore,
+// mnRelocQuery, mnRelocWords, mRelocScore, GetConnectedKeyFrames(),
+// GetBestCovisibilityKeyFrames(int); FR::mnId, mBowVec.
+template <class KF, class FR>
+class KeyFrameDatabase {
+ public:
+  explicit KeyFrameDatabase(const ORBVocabulary& voc) : mpVoc(&voc) {
+    orbx_throw(orbv_db_create(voc.Orbv(), 0, 0, &db_), "KeyFrameDatabase");
+  }
+  ~KeyFrameDatabase() { orbv_db_destroy(db_); }
+  KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+  void add(KF* pKF) {  // :20-26
+    std::unique_lock<std::mutex> lock(mMutex);
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    ORBVocabulary::Flatten(pKF->mBowVec, w, v);
+    orbx_throw(orbv_db_add(db_, (uint64_t)pKF->mnId, w.data(), v.data(), (int)w.size()), "KeyFrameDatabase::add");
+    kfs_[(uint64_t)pKF->mnId] = pKF;
+  }
+  void erase(KF* pKF) {  // :28-47
+    std::unique_lock<std::mutex> lock(mMutex);
+    typename std::map<uint64_t, KF*>::iterator it = kfs_.find((uint64_t)pKF->mnId);
+    if (it == kfs_.end() || it->second != pKF) return;
+    orbx_throw(orbv_db_erase(db_, (uint64_t)pKF->mnId), "KeyFrameDatabase::erase");
+    kfs_.erase(it);
+  }
+  void clear() {  // :49-53
+    std::unique_lock<std::mutex> lock(mMutex);
+    orbx_throw(orbv_db_clear(db_), "KeyFrameDatabase::clear");
+    kfs_.clear();
+  }
+
+  // :56-177
+  std::vector<KF*> DetectLoopCandidates(KF* pKF, float minScore) {
+    std::set<KF*> spConnectedKeyFrames = pKF->GetConnectedKeyFrames();
+    std::list<Sharing> lKFsSharingWords;
+    {
+      std::unique_lock<std::mutex> lock(mMutex);
+      std::vector<Sharing> all;
+      Query(pKF->mBowVec, all);
+      // the walk's marks, one keyframe's encounters at a time (its marks
+      // depend on no other keyframe's)
+      for (size_t i = 0; i < all.size(); ++i) {
+        KF* pKFi = all[i].kf;
+        if (pKFi->mnLoopQuery != pKF->mnId) {
+          if (!spConnectedKeyFrames.count(pKFi)) {
+            pKFi->mnLoopWords = all[i].ncommon;  // reset at the first encounter, counted at each
+            pKFi->mnLoopQuery = pKF->mnId;
+            lKFsSharingWords.push_back(all[i]);
+          } else {
+            pKFi->mnLoopWords = 1;  // never stamped: every encounter resets it, the last leaves 1
+          }
+        } else {
+          pKFi->mnLoopWords += all[i].ncommon;  // stamped by an earlier call with this id
+        }
+      }
+    }
+    if (lKFsSharingWords.empty()) return std::vector<KF*>();
+
+    std::list<std::pair<float, KF*> > lScoreAndMatch;
+    int maxCommonWords = 0;
+    for (typename std::list<Sharing>::iterator lit = lKFsSharingWords.begin(); lit != lKFsSharingWords.end(); lit++)
+      if (lit->kf->mnLoopWords > maxCommonWords) maxCommonWords = lit->kf->mnLoopWords;
+    int minCommonWords = maxCommonWords * 0.8f;
+
+    for (typename std::list<Sharing>::iterator lit = lKFsSharingWords.begin(); lit != lKFsSharingWords.end(); lit++) {
+      KF* pKFi = lit->kf;
+      if (pKFi->mnLoopWords > minCommonWords) {
+        float si = lit->score;
+        pKFi->mLoopScore = si;
+        if (si >= minScore) lScoreAndMatch.push_back(std::make_pair(si, pKFi));
+      }
+    }
+    if (lScoreAndMatch.empty()) return std::vector<KF*>();
+
+    std::list<std::pair<float, KF*> > lAccScoreAndMatch;
+    float bestAccScore = minScore;
+    for (typename std::list<std::pair<float, KF*> >::iterator it = lScoreAndMatch.begin();
+         it != lScoreAndMatch.end(); it++) {
+      KF* pKFi = it->second;
+      std::vector<KF*> vpNeighs = pKFi->GetBestCovisibilityKeyFrames(10);
+      float bestScore = it->first;
+      float accScore = it->first;
+      KF* pBestKF = pKFi;
+      for (typename std::vector<KF*>::iterator vit = vpNeighs.begin(); vit != vpNeighs.end(); vit++) {
+        KF* pKF2 = *vit;
+        if (pKF2->mnLoopQuery == pKF->mnId && pKF2->mnLoopWords > minCommonWords) {
+          accScore += pKF2->mLoopScore;
+          if (pKF2->mLoopScore > bestScore) {
+            pBestKF = pKF2;
+            bestScore = pKF2->mLoopScore;
+          }
+        }
+      }
+      lAccScoreAndMatch.push_back(std::make_pair(accScore, pBestKF));
+      if (accScore > bestAccScore) bestAccScore = accScore;
+    }
+    return Retain(lAccScoreAndMatch, 0.75f * bestAccScore);
+  }
+
+  // :179-289
+  std::vector<KF*> DetectRelocalizationCandidates(FR* F) {
+    std::list<Sharing> lKFsSharingWords;
+    {
+      std::unique_lock<std::mutex> lock(mMutex);
+      std::vector<Sharing> all;
+      Query(F->mBowVec, all);
+      for (size_t i = 0; i < all.size(); ++i) {
+        KF* pKFi = all[i].kf;
+        if (pKFi->mnRelocQuery != F->mnId) {
+          pKFi->mnRelocWords = all[i].ncommon;
+          pKFi->mnRelocQuery = F->mnId;
+          lKFsSharingWords.push_back(all[i]);
+        } else {
+          pKFi->mnRelocWords += all[i].ncommon;
+        }
+      }
+    }
+    if (lKFsSharingWords.empty()) return std::vector<KF*>();
+
+    int maxCommonWords = 0;
+    for (typename std::list<Sharing>::iterator lit = lKFsSharingWords.begin(); lit != lKFsSharingWords.end(); lit++)
+      if (lit->kf->mnRelocWords > maxCommonWords) maxCommonWords = lit->kf->mnRelocWords;
+    int minCommonWords = maxCommonWords * 0.8f;
+
+    std::list<std::pair<float, KF*> > lScoreAndMatch;
+    for (typename std::list<Sharing>::iterator lit = lKFsSharingWords.begin(); lit != lKFsSharingWords.end(); lit++) {
+      KF* pKFi = lit->kf;
+      if (pKFi->mnRelocWords > minCommonWords) {
+        float si = lit->score;
+        pKFi->mRelocScore = si;
+        lScoreAndMatch.push_back(std::make_pair(si, pKFi));
+      }
+    }
+    if (lScoreAndMatch.empty()) return std::vector<KF*>();
+
+    std::list<std::pair<float, KF*> > lAccScoreAndMatch;
+    float bestAccScore = 0;
+    for (typename std::list<std::pair<float, KF*> >::iterator it = lScoreAndMatch.begin();
+         it != lScoreAndMatch.end(); it++) {
+      KF* pKFi = it->second;
+      std::vector<KF*> vpNeighs = pKFi->GetBestCovisibilityKeyFrames(10);
+      float bestScore = it->first;
+      float accScore = bestScore;
+      KF* pBestKF = pKFi;
+      for (typename std::vector<KF*>::iterator vit = vpNeighs.begin(); vit != vpNeighs.end(); vit++) {
+        KF* pKF2 = *vit;
+        if (pKF2->mnRelocQuery != F->mnId) continue;
+        accScore += pKF2->mRelocScore;  // whatever it holds, also under the word gate
+        if (pKF2->mRelocScore > bestScore) {
+          pBestKF = pKF2;
+          bestScore = pKF2->mRelocScore;
+        }
+      }
+      lAccScoreAndMatch.push_back(std::make_pair(accScore, pBestKF));
+      if (accScore > bestAccScore) bestAccScore = accScore;
+    }
+    return Retain(lAccScoreAndMatch, 0.75f * bestAccScore);
+  }
+
+ protected:
+  struct Sharing {
+    KF* kf;
+    int ncommon;
+    double score;
+  };
+
+  // every stored keyframe sharing a word with `bow`, in the walk's order
+  void Query(const DBoW2::BowVector& bow, std::vector<Sharing>& out) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    ORBVocabulary::Flatten(bow, w, v);
+    const size_t cap = kfs_.size();
+    std::vector<uint64_t> id(cap);
+    std::vector<int32_t> nc(cap);
+    std::vector<double> sc(cap);
+    int n = 0;
+    orbx_throw(orbv_db_query(db_, w.data(), v.data(), (int)w.size(), (int)cap, id.data(), nc.data(), sc.data(), &n),
+               "KeyFrameDatabase: query");
+    out.clear();
+    for (int i = 0; i < n; ++i) {
+      Sharing s = {kfs_[id[i]], nc[i], sc[i]};
+      out.push_back(s);
+    }
+  }
+  // all those with an accumulated score above the bar, each once, first seen first
+  static std::vector<KF*> Retain(const std::list<std::pair<float, KF*> >& lAccScoreAndMatch, float minScoreToRetain) {
+    std::set<KF*> spAlreadyAddedKF;
+    std::vector<KF*> vpCandidates;
+    vpCandidates.reserve(lAccScoreAndMatch.size());
+    for (typename std::list<std::pair<float, KF*> >::const_iterator it = lAccScoreAndMatch.begin();
+         it != lAccScoreAndMatch.end(); it++) {
+      if (it->first > minScoreToRetain) {
+        KF* pKFi = it->second;
+        if (!spAlreadyAddedKF.count(pKFi)) {
+          vpCandidates.push_back(pKFi);
+          spAlreadyAddedKF.insert(pKFi);
+        }
+      }
+    }
+    return vpCandidates;
+  }
+
+  const ORBVocabulary* mpVoc;
+  orbv_db* db_ = nullptr;
+  std::map<uint64_t, KF*> kfs_;  // mnId -> keyframe, for the ids the store returns
+  std::mutex mMutex;
 };
 
 // Frame::ComputeStereoMatches (src/Frame.cc:446-620) for a stereo Frame whose

@@ -23,6 +23,7 @@ __global__ void k_bow_descend(const uint8_t*, const int*, int, const int*, const
                               const uint8_t*, const uint32_t*, const double*, int, BowRes*);
 __global__ void k_bow_assemble(const BowRes*, const int*, int, int, int, int, int, uint32_t*,
                                double*, int*, uint32_t*, uint32_t*, uint32_t*, int*, int*);
+int vocab_device(const orbv_vocab* v);
 }  // namespace orbx
 
 using namespace orbx;
@@ -191,6 +192,9 @@ extern "C" int orbv_vocab_destroy(orbv_vocab* v) {
   delete v;
   return ORBX_OK;
 }
+
+/* the device a vocabulary's tables live on (api_bowdb.hip: orbv_score) */
+int orbx::vocab_device(const orbv_vocab* v) { return v->device; }
 
 extern "C" int orbv_vocab_info(const orbv_vocab* v, int* k, int* L, int* scoring,
                                int* weighting, int* nnodes, int* nwords) {

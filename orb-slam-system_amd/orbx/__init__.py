@@ -66,6 +66,8 @@ EXPORTED = [
     "orbm_compute_distinctive_descriptors", "orbx_undistort_keypoints", "orbx_selftest_sincos",
     "orbx_selftest_sincos_range", "orbm_search_for_triangulation", "orbm_keyframe_search",
     "orbm_search_for_initialization", "orbm_search_for_initialization_stats",
+    "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_erase", "orbv_db_clear",
+    "orbv_db_size", "orbv_db_query",
 ]
 
 
@@ -219,6 +221,14 @@ _sig = {
     "orbv_transform": (I, [P, P, I, I, P, P, P, P, P, P, P]),
     "orbv_transform_batch": (I, [P, I, P, P, I, I, P, P, P, P, P, P, P, P]),
     "orbv_check": (I, [P, P]),
+    "orbv_score": (I, [P, P, P, I, P, P, P, I, P]),
+    "orbv_db_create": (I, [P, SZ, I, P]),
+    "orbv_db_destroy": (I, [P]),
+    "orbv_db_add": (I, [P, ctypes.c_uint64, P, P, I]),
+    "orbv_db_erase": (I, [P, ctypes.c_uint64]),
+    "orbv_db_clear": (I, [P]),
+    "orbv_db_size": (I, [P, P]),
+    "orbv_db_query": (I, [P, P, P, I, I, P, P, P, P]),
     "orbm_search_by_projection": (I, [I, P, P, P, I, F, I, I, I, P, P]),
     "orbm_proj_plan_create": (I, [I, I, I, I, P]),
     "orbm_proj_plan_destroy": (I, [P]),
@@ -471,6 +481,72 @@ class Vocabulary:
 
     def check(self, stream=None):
         _check(_lib.orbv_check(self._h, _stream_handle(stream)), "orbv_check")
+
+    def score(self, a, list_of_b):
+        """TemplatedVocabulary::score(a, b) for every b of the list, with the
+        vocabulary's scoring: BowVectors as (words u32 ascending, values f64)
+        -> f64[len(list_of_b)]"""
+        aw, av = _bow_vector(a)
+        bs = [_bow_vector(b) for b in list_of_b]
+        off = np.zeros(len(bs) + 1, np.uint32)
+        off[1:] = np.cumsum([len(w) for w, _ in bs])
+        bw = np.concatenate([w for w, _ in bs]) if bs else np.zeros(0, np.uint32)
+        bv = np.concatenate([v for _, v in bs]) if bs else np.zeros(0, np.float64)
+        out = np.zeros(len(bs), np.float64)
+        _check(_lib.orbv_score(self._h, _p(aw), _p(av), len(aw), _p(off), _p(bw), _p(bv), len(bs), _p(out)),
+               "orbv_score")
+        return out
+
+
+def _bow_vector(b):
+    w = np.ascontiguousarray(b[0], np.uint32).reshape(-1)
+    v = np.ascontiguousarray(b[1], np.float64).reshape(-1)
+    if len(w) != len(v):
+        raise OrbxError(ERR_ARG, "BowVector: one value per word expected")
+    return w, v
+
+
+class KeyFrameDatabase:
+    """The reference's KeyFrameDatabase inverted file on the device
+    (src/KeyFrameDatabase.cc): stored BowVectors keyed by keyframe id; query()
+    is the word walk of DetectLoopCandidates / DetectRelocalizationCandidates
+    with the scores."""
+
+    def __init__(self, vocabulary, reserve_words=0, device=0):
+        h = ctypes.c_void_p()
+        _check(_lib.orbv_db_create(vocabulary._h, reserve_words, device, ctypes.byref(h)), "orbv_db_create")
+        self._h = h
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.orbv_db_destroy(self._h)
+            self._h = None
+
+    def add(self, kf_id, bow):
+        w, v = _bow_vector(bow)
+        _check(_lib.orbv_db_add(self._h, kf_id, _p(w), _p(v), len(w)), "orbv_db_add")
+
+    def erase(self, kf_id):
+        _check(_lib.orbv_db_erase(self._h, kf_id), "orbv_db_erase")
+
+    def clear(self):
+        _check(_lib.orbv_db_clear(self._h), "orbv_db_clear")
+
+    def size(self):
+        n = ctypes.c_int()
+        _check(_lib.orbv_db_size(self._h, ctypes.byref(n)), "orbv_db_size")
+        return n.value
+
+    def query(self, bow):
+        """-> (ids u64, ncommon i32, score f64) of every stored keyframe sharing
+        a word with `bow`, in the order of the reference's lKFsSharingWords"""
+        w, v = _bow_vector(bow)
+        cap = max(self.size(), 1)
+        ids, nc, sc = np.zeros(cap, np.uint64), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
+        n = ctypes.c_int()
+        _check(_lib.orbv_db_query(self._h, _p(w), _p(v), len(w), cap, _p(ids), _p(nc), _p(sc), ctypes.byref(n)),
+               "orbv_db_query")
+        return ids[:n.value].copy(), nc[:n.value].copy(), sc[:n.value].copy()
 
 
 # --------------------------------------------------------------------------- ORBmatcher
