@@ -32,7 +32,8 @@ extern "C" {
  * orbm_keyframe_search, and orbx_init_pair and
  * orbm_search_for_initialization, and the debug entry points
  * orbx_debug_live_resources / orbx_debug_fail_acquire, and orbv_score and the
- * orbv_db_* keyframe database, are additive (no existing struct or entry
+ * orbv_db_* keyframe database with its batched queries
+ * (orbv_db_query_batch / orbv_db_query_batch_device), are additive (no existing struct or entry
  * point changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
@@ -608,6 +609,40 @@ int orbv_db_size(const orbv_db* db, int* nkf);
  * required count.  n == 0 or an empty database: ORBX_OK with *nsharing = 0. */
 int orbv_db_query(orbv_db* db, const uint32_t* word, const double* value, int n, int cap,
                   uint64_t* kf_id, int32_t* ncommon, double* score, int* nsharing);
+
+#define ORBV_QUERY_GATED 1  /* keep only entries with ncommon > (int)(maxCommonWords * 0.8f) */
+
+/* nq queries in CSR form: query q is q_word/q_value[q_off[q] .. q_off[q+1]), q_off[0] == 0.
+ * Result in CSR form: query q's entries are [out_off[q], out_off[q+1]) of kf_id / ncommon / score,
+ * each segment exactly what orbv_db_query returns for that query (same ids, order, counts,
+ * score bits).  With ORBV_QUERY_GATED the segment is that list with the entries whose
+ * ncommon <= (int)(max ncommon of the segment * 0.8f) removed, order kept:
+ * KeyFrameDatabase.cc:207-233 with nothing excluded.
+ * cap = entries the three arrays hold in total.  ORBX_ERR_CAPACITY: out_off[] is filled with the
+ * required offsets (out_off[nq] = required total) and no entry is written.  out_off (nq + 1
+ * entries) is always required and filled; nq == 0, empty queries and an empty database give
+ * ORBX_OK with empty segments.  ORBX_ERR_ARG for unknown flag bits, q_off[0] != 0, a descending
+ * q_off or words not strictly ascending below nwords; ORBX_ERR_UNSUPPORTED for a query of more
+ * than 8192 words or nq * (slots in the store) >= 2^31.  Synchronous, host buffers. */
+int orbv_db_query_batch(orbv_db* db, int nq, const uint32_t* q_off, const uint32_t* q_word,
+                        const double* q_value, int flags, int cap, uint32_t* out_off,
+                        uint64_t* kf_id, int32_t* ncommon, double* score);
+
+/* The same on device buffers, asynchronous on `stream`.
+ * Queries: [nq][qstride] with d_n[nq], the layout of orbv_transform_batch's d_bow_word /
+ * d_bow_value / d_nbow with qstride = kcap (qstride > 8192: ORBX_ERR_UNSUPPORTED).
+ * d_n[q] < 0 counts as 0; d_n[q] > qstride gives d_nsharing[q] = -1 and nothing written for q.
+ * The words are taken as orbv_transform_batch emits them (strictly ascending, below nwords) and
+ * are NOT checked: other words give a wrong list, never an access out of range.
+ * Outputs: [nq][cap], and d_nsharing[nq] = the full count.  Entries beyond cap are not written.
+ * For L2_NORM d_score holds the sum s before the scoring's closing step, which the caller
+ * applies: score = s >= 1 ? 1.0 : 1.0 - sqrt(1.0 - s) (the host forms apply it themselves).
+ * The call leaves work in flight that reads the store and the handle's scratch: a later call of
+ * this form on another stream waits for it on the device, every other orbv_db_* call on the
+ * host.  The caller keeps its buffers alive until `stream` has run the work. */
+int orbv_db_query_batch_device(orbv_db* db, int nq, const uint32_t* d_word, const double* d_value,
+                               const int* d_n, int qstride, int flags, int cap, uint64_t* d_kf_id,
+                               int32_t* d_ncommon, double* d_score, int* d_nsharing, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Projection matchers: the frame grid

@@ -1025,7 +1025,9 @@ class ORBVocabulary {
 // is the device store behind orbv_db: add / erase / clear keep it, and one
 // orbv_db_query per Detect*Candidates call returns what the reference's walk
 // over mvInvertedFile collects -- every keyframe sharing a word, in
-// lKFsSharingWords' order, with its number of common words and its score.
+// lKFsSharingWords' order, with its number of common words and its score
+// (the vector form of DetectRelocalizationCandidates: one
+// orbv_db_query_batch for all its frames).
 // Everything after the walk needs the caller's graph and runs here on that
 // list as the reference words it, reading and writing exactly the members the
 // reference does: KF::mnId, mBowVec, mnLoopQuery, mnLoopWords, mLoopScore,
@@ -1132,11 +1134,50 @@ class KeyFrameDatabase {
 
   // :179-289
   std::vector<KF*> DetectRelocalizationCandidates(FR* F) {
+    std::vector<Sharing> all;
+    {
+      std::unique_lock<std::mutex> lock(mMutex);
+      Query(F->mBowVec, all);
+    }
+    return RelocalizationCandidates(F, all);
+  }
+
+  // The same for a batch of lost frames (a relocalisation sweep): one ungated
+  // orbv_db_query_batch for all of them, then the host step frame after frame
+  // in list order.  This equals calling the single form on vpF[0], vpF[1],
+  // ... in turn: the search reads none of the members the host step writes
+  // (mnRelocQuery, mnRelocWords, mRelocScore), so every frame's list is the
+  // one its own call would have fetched -- provided no keyframe is added or
+  // erased while the call runs, which the single calls would have seen
+  // between frames.  The list is fetched ungated: the host step stamps
+  // mnRelocQuery / mnRelocWords on every sharing keyframe, the ones under the
+  // word gate included, and a later frame's accumulation reads them.
+  std::vector<std::vector<KF*> > DetectRelocalizationCandidates(const std::vector<FR*>& vpF) {
+    std::vector<std::vector<Sharing> > all;
+    {
+      std::unique_lock<std::mutex> lock(mMutex);
+      std::vector<const DBoW2::BowVector*> bows;
+      for (size_t f = 0; f < vpF.size(); ++f) bows.push_back(&vpF[f]->mBowVec);
+      QueryBatch(bows, all);
+    }
+    std::vector<std::vector<KF*> > vvpCandidates;
+    vvpCandidates.reserve(vpF.size());
+    for (size_t f = 0; f < vpF.size(); ++f) vvpCandidates.push_back(RelocalizationCandidates(vpF[f], all[f]));
+    return vvpCandidates;
+  }
+
+ protected:
+  struct Sharing {
+    KF* kf;
+    int ncommon;
+    double score;
+  };
+
+  // :181-289 on the walk's result `all`
+  std::vector<KF*> RelocalizationCandidates(FR* F, const std::vector<Sharing>& all) {
     std::list<Sharing> lKFsSharingWords;
     {
       std::unique_lock<std::mutex> lock(mMutex);
-      std::vector<Sharing> all;
-      Query(F->mBowVec, all);
       for (size_t i = 0; i < all.size(); ++i) {
         KF* pKFi = all[i].kf;
         if (pKFi->mnRelocQuery != F->mnId) {
@@ -1190,13 +1231,6 @@ class KeyFrameDatabase {
     return Retain(lAccScoreAndMatch, 0.75f * bestAccScore);
   }
 
- protected:
-  struct Sharing {
-    KF* kf;
-    int ncommon;
-    double score;
-  };
-
   // every stored keyframe sharing a word with `bow`, in the walk's order
   void Query(const DBoW2::BowVector& bow, std::vector<Sharing>& out) {
     std::vector<uint32_t> w;
@@ -1214,6 +1248,40 @@ class KeyFrameDatabase {
       Sharing s = {kfs_[id[i]], nc[i], sc[i]};
       out.push_back(s);
     }
+  }
+  // the same for several BowVectors in one orbv_db_query_batch: out[f] is
+  // what Query(*bows[f], ..) gives
+  void QueryBatch(const std::vector<const DBoW2::BowVector*>& bows, std::vector<std::vector<Sharing> >& out) {
+    std::vector<uint32_t> off(bows.size() + 1, 0u), w;
+    std::vector<double> v;
+    for (size_t f = 0; f < bows.size(); ++f) {
+      ORBVocabulary::Flatten(*bows[f], w, v);
+      off[f + 1] = (uint32_t)w.size();
+    }
+    std::vector<uint32_t> seg(bows.size() + 1, 0u);
+    size_t cap = kfs_.size();  // most frames share with a part of the map; the call says when it needs more
+    std::vector<uint64_t> id;
+    std::vector<int32_t> nc;
+    std::vector<double> sc;
+    for (int attempt = 0;; ++attempt) {
+      id.resize(cap);
+      nc.resize(cap);
+      sc.resize(cap);
+      const int rc = orbv_db_query_batch(db_, (int)bows.size(), off.data(), w.data(), v.data(), 0, (int)cap, seg.data(),
+                                         id.data(), nc.data(), sc.data());
+      if (rc == ORBX_ERR_CAPACITY && attempt == 0) {
+        cap = seg[bows.size()];
+        continue;
+      }
+      orbx_throw(rc, "KeyFrameDatabase: batched query");
+      break;
+    }
+    out.assign(bows.size(), std::vector<Sharing>());
+    for (size_t f = 0; f < bows.size(); ++f)
+      for (uint32_t i = seg[f]; i < seg[f + 1]; ++i) {
+        Sharing s = {kfs_[id[i]], nc[i], sc[i]};
+        out[f].push_back(s);
+      }
   }
   // all those with an accumulated score above the bar, each once, first seen first
   static std::vector<KF*> Retain(const std::list<std::pair<float, KF*> >& lAccScoreAndMatch, float minScoreToRetain) {

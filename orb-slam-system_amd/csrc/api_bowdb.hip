@@ -18,6 +18,10 @@
 namespace orbx {
 __global__ void k_bowdb_query(const uint32_t*, const double*, int, const BowdbSlot*, int, const uint32_t*,
                               const double*, int, BowdbRec*);
+__global__ void k_bowdb_query_batch(const uint32_t*, const int*, int, const uint32_t*, const double*, int,
+                                    const BowdbSlot*, int, const uint32_t*, const double*, int, BowdbBatchRec*);
+__global__ void k_bowdb_order(const BowdbBatchRec*, const BowdbSlot*, int, int, const uint32_t*, const int*, int, int,
+                              int, int, int*, uint64_t*, int32_t*, double*, int*);
 int vocab_device(const orbv_vocab* v);  // api_bow.hip
 }  // namespace orbx
 
@@ -33,8 +37,18 @@ struct orbv_db {
   size_t slot_cap = 0;
   bool dirty = false;  // the host's slot table is ahead of d_slots
   Stream stream;       // growth, compaction and the slot table's upload
+  // the batched queries' scratch, acquired at the first batched call: one
+  // record per (query, slot), grown by doubling; and the event recorded behind
+  // the device form's last kernel, which reads the store and this scratch
+  DevBuf<BowdbBatchRec> d_rec;
+  size_t rec_cap = 0;
+  Event done;
+  bool inflight = false;  // `done` was recorded and not waited for on the host
   explicit orbv_db(size_t reserve) : table(reserve) {}
-  ~orbv_db() { hipSetDevice(device); }
+  ~orbv_db() {
+    hipSetDevice(device);
+    if (inflight) (void)hipEventSynchronize(done);
+  }
 };
 
 namespace {
@@ -89,6 +103,51 @@ int upload_slots(orbv_db* db) {
   }
   db->dirty = false;
   return ORBX_OK;
+}
+
+// the host's wait for the device form's work in flight, before anything it
+// reads is touched or released
+int wait_inflight(orbv_db* db) {
+  if (!db->inflight) return ORBX_OK;
+  ORBX_TRY(hipSetDevice(db->device));
+  ORBX_TRY(hipEventSynchronize(db->done));
+  db->inflight = false;
+  return ORBX_OK;
+}
+
+// the batched calls' scratch: the event, and room for `nrec` records
+int ensure_batch_scratch(orbv_db* db, size_t nrec) {
+  if (!db->done && db->done.create(hipEventDisableTiming)) return ORBX_ERR_HIP;
+  if (nrec <= db->rec_cap && db->d_rec) return ORBX_OK;
+  const int rc = wait_inflight(db);  // the old scratch may be in use
+  if (rc) return rc;
+  size_t c = db->rec_cap ? db->rec_cap : 4096;
+  while (c < nrec) c *= 2;
+  db->rec_cap = 0;
+  if (db->d_rec.alloc(c)) return ORBX_ERR_HIP;
+  db->rec_cap = c;
+  return ORBX_OK;
+}
+
+// the two kernels of a batched call on stream s.  Query layout: see
+// kernels_bowdb.hip.  lds_words: the longest query the layout allows
+void launch_query_batch(hipStream_t s, const orbv_db* db, int nq, int nslots, const uint32_t* q_off, const int* d_n,
+                        int qstride, const uint32_t* qw, const double* qv, int lds_words) {
+  if (nslots == 0) return;
+  // about 2048 workgroups in all: few queries spread over the slots as the
+  // single query does, many queries stage each query's words a few times only
+  const int bx = std::min((nslots + 3) / 4, std::max(1, (2048 + nq - 1) / nq));
+  hipLaunchKernelGGL(k_bowdb_query_batch, dim3(bx, std::min(nq, 65535)), dim3(256),
+                     (size_t)lds_words * sizeof(uint32_t), s, q_off, d_n, qstride, qw, qv, nq, db->d_slots, nslots,
+                     db->d_words, db->d_values, db->scoring, db->d_rec);
+}
+
+void launch_order(hipStream_t s, const orbv_db* db, int nq, int nslots, const uint32_t* q_off, const int* d_n,
+                  int qstride, int lds_words, int flags, int mode, int cap, int* cnt, uint64_t* kf_id,
+                  int32_t* ncommon, double* score, int* nsharing) {
+  hipLaunchKernelGGL(k_bowdb_order, dim3(std::min(nq, 65535)), dim3(BOWDB_ORDER_TILE),
+                     (size_t)lds_words * sizeof(uint32_t), s, db->d_rec, db->d_slots, nslots, nq, q_off, d_n, qstride,
+                     (flags & ORBV_QUERY_GATED) ? 1 : 0, mode, cap, cnt, kf_id, ncommon, score, nsharing);
 }
 
 }  // namespace
@@ -166,6 +225,7 @@ extern "C" int orbv_db_add(orbv_db* db, uint64_t kf_id, const uint32_t* word, co
   if (bowdb_check_words(word, n, db->nwords) || db->table.contains(kf_id)) return ORBX_ERR_ARG;
   if (db->table.used() + (size_t)n > 0xFFFFFFFFull) return ORBX_ERR_UNSUPPORTED;  // 32-bit offsets
   ORBX_TRY(hipSetDevice(db->device));
+  if (wait_inflight(db)) return ORBX_ERR_HIP;
   const size_t cap = db->table.capacity_for((size_t)n);
   if (cap > db->table.capacity()) {
     std::vector<BowdbMove> whole;
@@ -195,6 +255,7 @@ extern "C" int orbv_db_add(orbv_db* db, uint64_t kf_id, const uint32_t* word, co
 
 extern "C" int orbv_db_erase(orbv_db* db, uint64_t kf_id) {
   if (!db) return ORBX_ERR_ARG;
+  if (wait_inflight(db)) return ORBX_ERR_HIP;
   if (!db->table.erase(kf_id)) return ORBX_OK;  // as list::erase never reached
   db->dirty = true;
   if (db->table.wants_compaction()) {
@@ -212,6 +273,7 @@ extern "C" int orbv_db_erase(orbv_db* db, uint64_t kf_id) {
 
 extern "C" int orbv_db_clear(orbv_db* db) {
   if (!db) return ORBX_ERR_ARG;
+  if (wait_inflight(db)) return ORBX_ERR_HIP;
   db->table.clear();
   db->dirty = true;
   return ORBX_OK;
@@ -231,6 +293,7 @@ extern "C" int orbv_db_query(orbv_db* db, const uint32_t* word, const double* va
   if (bowdb_check_words(word, n, db->nwords)) return ORBX_ERR_ARG;
   if (n == 0 || db->table.nkf() == 0) return ORBX_OK;
   ORBX_TRY(hipSetDevice(db->device));
+  if (wait_inflight(db)) return ORBX_ERR_HIP;
   if (db->dirty) {
     const int rc = upload_slots(db);
     if (rc) return rc;
@@ -265,5 +328,90 @@ extern "C" int orbv_db_query(orbv_db* db, const uint32_t* word, const double* va
     ncommon[i] = r.ncommon;
     score[i] = close_score(db->scoring, r.score);
   }
+  return ORBX_OK;
+}
+
+extern "C" int orbv_db_query_batch(orbv_db* db, int nq, const uint32_t* q_off, const uint32_t* q_word,
+                                   const double* q_value, int flags, int cap, uint32_t* out_off, uint64_t* kf_id,
+                                   int32_t* ncommon, double* score) {
+  if (!db || nq < 0 || cap < 0 || (flags & ~ORBV_QUERY_GATED) || !out_off) return ORBX_ERR_ARG;
+  const int ok = bowdb_check_batch(nq, q_off, q_word, q_value, db->nwords);
+  if (ok) return ok;
+  const int nslots = (int)db->table.slots().size();
+  if ((uint64_t)nq * (uint64_t)nslots >= 0x80000000ull) return ORBX_ERR_UNSUPPORTED;
+  for (int q = 0; q <= nq; ++q) out_off[q] = 0;
+  if (nq == 0 || q_off[nq] == 0 || db->table.nkf() == 0) return ORBX_OK;
+  ORBX_TRY(hipSetDevice(db->device));
+  if (wait_inflight(db)) return ORBX_ERR_HIP;
+  if (db->dirty) {
+    const int rc = upload_slots(db);
+    if (rc) return rc;
+  }
+  int rc = ensure_batch_scratch(db, (size_t)nq * (size_t)nslots);
+  if (rc) return rc;
+  int longest = 0;
+  for (int q = 0; q < nq; ++q) longest = std::max(longest, (int)(q_off[q + 1] - q_off[q]));
+  // the queries up, the counts down
+  CallArena A(db->device);
+  if (!A.ok()) return ORBX_ERR_HIP;
+  auto qo = A.in(q_off, (size_t)nq + 1);
+  auto qw = A.in(q_word, (size_t)q_off[nq]);
+  auto qv = A.in(q_value, (size_t)q_off[nq]);
+  auto cnt = A.out<int>(nullptr, (size_t)nq);
+  if (A.commit() || A.upload()) return ORBX_ERR_HIP;
+  launch_query_batch(A.stream(), db, nq, nslots, A.d(qo), nullptr, 0, A.d(qw), A.d(qv), longest);
+  launch_order(A.stream(), db, nq, nslots, A.d(qo), nullptr, 0, longest, flags, 0, 0, A.d(cnt), nullptr, nullptr,
+               nullptr, nullptr);
+  rc = A.finish();
+  if (rc) return rc;
+  const uint64_t total = bowdb_pack_offsets(A.h(cnt), nq, out_off);
+  if (total > (uint64_t)cap) return ORBX_ERR_CAPACITY;
+  if (total == 0) return ORBX_OK;
+  if (!kf_id || !ncommon || !score) return ORBX_ERR_ARG;
+  // the entries in use down: placed by a second pass of the order kernel, which
+  // reads the counts and the offsets where the first arena still holds them
+  CallArena B(db->device);
+  if (!B.ok()) return ORBX_ERR_HIP;
+  auto oid = B.out(kf_id, (size_t)total);
+  auto onc = B.out(ncommon, (size_t)total);
+  auto osc = B.out<double>(nullptr, (size_t)total);
+  if (B.commit()) return ORBX_ERR_HIP;
+  launch_order(B.stream(), db, nq, nslots, A.d(qo), nullptr, 0, longest, flags, 1, 0, A.d(cnt), B.d(oid), B.d(onc),
+               B.d(osc), nullptr);
+  rc = B.finish();
+  if (rc) return rc;
+  const double* hs = B.h(osc);
+  for (uint64_t i = 0; i < total; ++i) score[i] = close_score(db->scoring, hs[i]);
+  return ORBX_OK;
+}
+
+extern "C" int orbv_db_query_batch_device(orbv_db* db, int nq, const uint32_t* d_word, const double* d_value,
+                                          const int* d_n, int qstride, int flags, int cap, uint64_t* d_kf_id,
+                                          int32_t* d_ncommon, double* d_score, int* d_nsharing, void* stream) {
+  if (!db || nq < 0 || cap < 0 || qstride < 0 || (flags & ~ORBV_QUERY_GATED)) return ORBX_ERR_ARG;
+  if (qstride > BOWDB_MAX_WORDS) return ORBX_ERR_UNSUPPORTED;
+  const int nslots = (int)db->table.slots().size();
+  if ((uint64_t)nq * (uint64_t)nslots >= 0x80000000ull) return ORBX_ERR_UNSUPPORTED;
+  if (nq == 0) return ORBX_OK;
+  if (!d_n || !d_nsharing || (qstride > 0 && (!d_word || !d_value)) ||
+      (cap > 0 && (!d_kf_id || !d_ncommon || !d_score)))
+    return ORBX_ERR_ARG;
+  ORBX_TRY(hipSetDevice(db->device));
+  if (db->dirty) {  // the slot table changes under whatever is in flight
+    if (wait_inflight(db)) return ORBX_ERR_HIP;
+    const int rc = upload_slots(db);
+    if (rc) return rc;
+  }
+  const int rc = ensure_batch_scratch(db, (size_t)nq * (size_t)nslots);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // an earlier call's kernels, on whichever stream, are done with the scratch first
+  if (db->inflight) ORBX_TRY(hipStreamWaitEvent(s, db->done, 0));
+  launch_query_batch(s, db, nq, nslots, nullptr, d_n, qstride, d_word, d_value, qstride);
+  launch_order(s, db, nq, nslots, nullptr, d_n, qstride, qstride, flags, 2, cap, nullptr, d_kf_id, d_ncommon, d_score,
+               d_nsharing);
+  ORBX_TRY(hipGetLastError());
+  ORBX_TRY(hipEventRecord(db->done, s));
+  db->inflight = true;
   return ORBX_OK;
 }

@@ -35,6 +35,18 @@ struct BowdbRec {
   uint32_t first;  // smallest common word
 };
 
+// what the batched query kernel writes per (query, slot) (16 bytes), record
+// q * nslots + j; ncommon == 0: not sharing / dead.  rank: the position in the
+// query of the smallest common word, below the query's length.  The rank is
+// monotone in the word, so (rank, j) orders as (first, j) does
+struct BowdbBatchRec {
+  double score;
+  int32_t ncommon;
+  uint32_t rank;
+};
+
+#define BOWDB_ORDER_TILE 256  /* slots per step of the order kernel's placement = its workgroup */
+
 // a run of the word store that compaction moves: [src, src + len) -> dst
 struct BowdbMove {
   size_t src, dst, len;
@@ -135,6 +147,42 @@ inline int bowdb_check_words(const uint32_t* word, int n, uint32_t nwords) {
   for (int i = 0; i < n; ++i)
     if (word[i] >= nwords || (i > 0 && word[i] <= word[i - 1])) return -1;
   return 0;
+}
+
+// The queries of a batched call in CSR form: query q is
+// q_word / q_value[q_off[q], q_off[q + 1]), q_off[0] == 0 and never descending,
+// every query's words as bowdb_check_words wants them.  ORBX_OK (0),
+// ORBX_ERR_ARG (-1), or ORBX_ERR_UNSUPPORTED (-6) for a query of more than
+// BOWDB_MAX_WORDS words; the first offending query decides
+inline int bowdb_check_batch(int nq, const uint32_t* q_off, const uint32_t* q_word, const double* q_value,
+                             uint32_t nwords) {
+  if (nq < 0) return -1;
+  if (nq == 0) return 0;
+  if (!q_off || q_off[0] != 0) return -1;
+  for (int q = 0; q < nq; ++q) {
+    if (q_off[q + 1] < q_off[q]) return -1;
+    const uint32_t len = q_off[q + 1] - q_off[q];
+    if (len > BOWDB_MAX_WORDS) return -6;
+    if (len > 0 && (!q_word || !q_value)) return -1;
+    if (len > 0 && bowdb_check_words(q_word + q_off[q], (int)len, nwords)) return -1;
+  }
+  return 0;
+}
+
+// minCommonWords of KeyFrameDatabase.cc:207-214 from the largest count: an
+// entry stays when its count is above it.  constexpr: the order kernel calls it
+constexpr int bowdb_gate(int max_common) { return (int)(max_common * 0.8f); }
+
+// the packed result's offsets from the per-query counts: out_off[0] = 0,
+// out_off[q + 1] = out_off[q] + cnt[q]; returns the total
+inline uint64_t bowdb_pack_offsets(const int* cnt, int nq, uint32_t* out_off) {
+  uint64_t at = 0;
+  out_off[0] = 0;
+  for (int q = 0; q < nq; ++q) {
+    at += (uint64_t)(cnt[q] > 0 ? cnt[q] : 0);
+    out_off[q + 1] = (uint32_t)at;
+  }
+  return at;
 }
 
 }  // namespace orbx

@@ -44,6 +44,7 @@ assert KEYPOINT_DTYPE.itemsize == 28
 
 OK, ERR_ARG, ERR_CELL_ROI, ERR_LEVEL_SIZE, ERR_QUADTREE, ERR_CAPACITY, ERR_UNSUPPORTED, \
     ERR_HIP, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6, -7, -8
+ORBV_QUERY_GATED = 1  # orbv_db_query_batch flags (include/orbx.h)
 ORBM_PLAN_ZERO_TAIL, ORBM_PLAN_VALU = 1, 2  # orbm_plan_set_options flags (include/orbx.h)
 ORBX_PLAN_PYR_TILES, ORBX_PLAN_BRIEF_PATCH, ORBX_PLAN_BRIEF_LEVEL, ORBX_PLAN_FAST_DENSE = 1, 8, 16, 64  # orbx_plan_set_options flags
 
@@ -67,7 +68,7 @@ EXPORTED = [
     "orbx_selftest_sincos_range", "orbm_search_for_triangulation", "orbm_keyframe_search",
     "orbm_search_for_initialization", "orbm_search_for_initialization_stats",
     "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_erase", "orbv_db_clear",
-    "orbv_db_size", "orbv_db_query",
+    "orbv_db_size", "orbv_db_query", "orbv_db_query_batch", "orbv_db_query_batch_device",
 ]
 
 
@@ -229,6 +230,8 @@ _sig = {
     "orbv_db_clear": (I, [P]),
     "orbv_db_size": (I, [P, P]),
     "orbv_db_query": (I, [P, P, P, I, I, P, P, P, P]),
+    "orbv_db_query_batch": (I, [P, I, P, P, P, I, I, P, P, P, P]),
+    "orbv_db_query_batch_device": (I, [P, I, P, P, P, I, I, I, P, P, P, P, P]),
     "orbm_search_by_projection": (I, [I, P, P, P, I, F, I, I, I, P, P]),
     "orbm_proj_plan_create": (I, [I, I, I, I, P]),
     "orbm_proj_plan_destroy": (I, [P]),
@@ -547,6 +550,57 @@ class KeyFrameDatabase:
         _check(_lib.orbv_db_query(self._h, _p(w), _p(v), len(w), cap, _p(ids), _p(nc), _p(sc), ctypes.byref(n)),
                "orbv_db_query")
         return ids[:n.value].copy(), nc[:n.value].copy(), sc[:n.value].copy()
+
+    def query_batch(self, bows, gated=False):
+        """query() for every BowVector of the list in one call -> a list of
+        (ids u64, ncommon i32, score f64); gated: each list keeps only the
+        entries with ncommon > int(max ncommon * 0.8f), order kept"""
+        qs = [_bow_vector(b) for b in bows]
+        off = np.zeros(len(qs) + 1, np.uint32)
+        off[1:] = np.cumsum([len(w) for w, _ in qs])
+        qw = np.concatenate([w for w, _ in qs]) if qs else np.zeros(0, np.uint32)
+        qv = np.concatenate([v for _, v in qs]) if qs else np.zeros(0, np.float64)
+        flags = ORBV_QUERY_GATED if gated else 0
+        out = np.zeros(len(qs) + 1, np.uint32)
+        cap = max(self.size(), 1)
+        for attempt in range(2):  # once more with the total the call asks for
+            ids, nc, sc = np.zeros(cap, np.uint64), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
+            rc = _lib.orbv_db_query_batch(self._h, len(qs), _p(off), _p(qw), _p(qv), flags, cap, _p(out), _p(ids),
+                                          _p(nc), _p(sc))
+            if rc != ERR_CAPACITY or attempt:
+                break
+            cap = int(out[-1])
+        _check(rc, "orbv_db_query_batch")
+        return [(ids[a:b].copy(), nc[a:b].copy(), sc[a:b].copy()) for a, b in zip(out[:-1].tolist(), out[1:].tolist())]
+
+    def query_batch_device(self, word, value, n, cap, gated=False, stream=None):
+        """Device form over Vocabulary.transform_batch outputs: word cuda i32
+        [B, qstride], value cuda f64 [B, qstride], n cuda i32 [B].  Async on
+        `stream`; returns dict of cuda tensors kf_id i64 [B, cap], ncommon i32
+        [B, cap], score f64 [B, cap] (for L2_NORM the sum before the closing
+        sqrt step) and nsharing i32 [B]: row q's first min(nsharing[q], cap)
+        entries are query()'s list, nsharing[q] == -1 for n[q] > qstride.  The
+        words are not checked."""
+        import torch
+        B, qstride = word.shape[0], word.shape[1]
+        dev = word.device
+        o = dict(kf_id=torch.empty((B, cap), dtype=torch.int64, device=dev),
+                 ncommon=torch.empty((B, cap), dtype=torch.int32, device=dev),
+                 score=torch.empty((B, cap), dtype=torch.float64, device=dev),
+                 nsharing=torch.empty(B, dtype=torch.int32, device=dev))
+        self.query_batch_device_into(word, value, n, o, gated, stream)
+        return o
+
+    def query_batch_device_into(self, word, value, n, out, gated=False, stream=None):
+        """query_batch_device into the tensors of an earlier call's dict"""
+        B, qstride = word.shape[0], word.shape[1]
+        cap = out["kf_id"].shape[1]
+        _check(_lib.orbv_db_query_batch_device(self._h, B, word.data_ptr(), value.data_ptr(), n.data_ptr(), qstride,
+                                               ORBV_QUERY_GATED if gated else 0, cap, out["kf_id"].data_ptr(),
+                                               out["ncommon"].data_ptr(), out["score"].data_ptr(),
+                                               out["nsharing"].data_ptr(), _stream_handle(stream)),
+               "orbv_db_query_batch_device")
+        return out
 
 
 # --------------------------------------------------------------------------- ORBmatcher
