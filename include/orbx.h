@@ -33,8 +33,10 @@ extern "C" {
  * orbm_search_for_initialization, and the debug entry points
  * orbx_debug_live_resources / orbx_debug_fail_acquire, and orbv_score and the
  * orbv_db_* keyframe database with its batched queries
- * (orbv_db_query_batch / orbv_db_query_batch_device), are additive (no existing struct or entry
- * point changes), so the version stays 2. */
+ * (orbv_db_query_batch / orbv_db_query_batch_device), and the device-side projection
+ * (orbx_proj_camera / orbx_proj_points / orbx_proj_params / orbx_proj_build_problem,
+ * orbm_predict_scale_thresholds, orbm_project_points, orbm_proj_plan_project / _track), are
+ * additive (no existing struct or entry point changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
 /* status codes */
@@ -648,10 +650,11 @@ int orbv_db_query_batch_device(orbv_db* db, int nq, const uint32_t* d_word, cons
  * Projection matchers: the frame grid
  * (Frame::AssignFeaturesToGrid / PosInGrid / GetFeaturesInArea,
  * src/Frame.cc:210-225,307-371, 64 x 48 cells) and the windowed Hamming
- * search of ORBmatcher::SearchByProjection.  Query form: the caller projects
- * (the cv::Mat pose arithmetic and MapPoint::PredictScale stay with the
- * caller) and passes per query the arguments the reference hands to
- * GetFeaturesInArea plus the gates' inputs.
+ * search of ORBmatcher::SearchByProjection.  Query form: per query the
+ * arguments the reference hands to GetFeaturesInArea plus the gates' inputs.
+ * The caller may project itself, or have the rows built on the device from
+ * map points and a pose (orbm_project_points / orbm_proj_plan_project /
+ * orbm_proj_plan_track below).
  * ------------------------------------------------------------------------- */
 typedef struct {
   float x, y;                    /* mTrackProjX/Y (mode 1) or the projection u, v       */
@@ -713,6 +716,114 @@ int orbm_proj_plan_create(int max_problems, int max_n, int max_nq, int device, o
 int orbm_proj_plan_destroy(orbm_proj_plan* plan);
 int orbm_proj_plan_search(orbm_proj_plan* plan, int mode, int nprob, const orbx_proj_problem* probs,
                           float nnratio, int th_dist, int check_ori, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Device-side projection for the three SearchByProjection forms: map points
+ * and a pose in, orbx_query_proj rows out.
+ *   mode 1: Frame::isInFrustum (src/Frame.cc:249-305) + the radius / levels of
+ *           SearchByProjection(Frame&, vector<MapPoint*>&, th) (:19-28,67-69)
+ *   mode 2: the projection of the last-frame form (:750-774)
+ *   mode 3: the projection of the keyframe form (:832-848)
+ * Point i writes query row i; there is no compaction.  Where the reference
+ * executes `continue` / `return false`, the row is inert: x = y = 0,
+ * radius = -1, min_level = max_level = -1, xr = angle = 0 and level[i] = -1.
+ * An inert row fails the matcher's strict box test for every feature, so it
+ * takes nothing and match[] of a search over these rows names the map point.
+ * The one deviation: a point the reference would hand to GetFeaturesInArea
+ * with a NaN / infinite u or v (it converts them to int), and a mode-2 octave
+ * outside [0, nlevels), is written inert and counted in n_nonfinite.
+ * ------------------------------------------------------------------------- */
+#define ORBX_PROJ_MAX_LEVELS 32
+typedef struct {
+  float Rcw[9], tcw[3];        /* rows 0..2 of mTcw: rotation (row-major), translation      */
+  float ow[3];                 /* camera centre: mOw (mode 1), twc (modes 2, 3); computed
+                                  by the caller once per frame                              */
+  float fx, fy, cx, cy, mbf;
+  float min_x, max_x, min_y, max_y; /* mnMinX, mnMaxX, mnMinY, mnMaxY                       */
+  int nlevels;                 /* mnScaleLevels, 1 .. ORBX_PROJ_MAX_LEVELS                  */
+  float scale_factors[ORBX_PROJ_MAX_LEVELS]; /* mvScaleFactors, nlevels used                */
+  float log_scale_factor;      /* mfLogScaleFactor: finite, > 0                             */
+} orbx_proj_camera;
+
+/* map points of one problem, npts entries per array; the arrays a mode does
+ * not read may be NULL */
+typedef struct {
+  const float* pos;           /* [npts][3] GetWorldPos()                                    */
+  const float* normal;        /* mode 1: [npts][3] GetNormal()                              */
+  const float* min_dist_inv;  /* mode 1: GetMinDistanceInvariance()                         */
+  const float* max_dist_inv;  /* mode 1: GetMaxDistanceInvariance()                         */
+  const float* max_dist;      /* modes 1, 3: the raw mfMaxDistance PredictScale divides
+                                 (not the x1.2 value)                                       */
+  const int32_t* octave;      /* mode 2: LastFrame.mvKeys[i].octave                         */
+  const float* angle;         /* mode 2: LastFrame.mvKeys[i].angle; mode 3: pKF->mvKeys[i]  */
+  const uint8_t* skip;        /* NULL = none; 1 where the reference skips the point before
+                                 projecting -- mode 1: mnLastFrameSeen == id or isBad();
+                                 mode 2: null or outlier; mode 3: null, bad or already found */
+} orbx_proj_points;
+
+enum { ORBX_LEVEL_RULE_NEITHER = 0, ORBX_LEVEL_RULE_FORWARD = 1, ORBX_LEVEL_RULE_BACKWARD = 2 };
+typedef struct {
+  float th;                /* the th argument of the reference call                          */
+  float viewing_cos_limit; /* mode 1: isInFrustum's second argument                          */
+  int level_rule;          /* mode 2: bForward / bBackward, evaluated by the caller          */
+} orbx_proj_params;
+
+/* thr[L], L = 0 .. nlevels - 2: the smallest positive float ratio for which
+ * MapPoint::PredictScale (src/MapPoint.cc:364-373: logf, divide, ceil,
+ * truncate, clamp) gives a level above L under this host's logf; +inf where no
+ * finite ratio does.  The kernels count thresholds instead of taking a
+ * logarithm.  ORBX_ERR_ARG for nlevels outside 1 .. ORBX_PROJ_MAX_LEVELS and a
+ * log_scale_factor that is not finite, is <= 0, or so small that
+ * logf(FLT_MAX) / log_scale_factor reaches 2^31. */
+int orbm_predict_scale_thresholds(float log_scale_factor, int nlevels, float* thr);
+
+/* nprob problems (problem p: cameras[p], points[p], npts[p]; `params` is
+ * shared) in one launch.  Host pointers; synchronous.  Outputs are
+ * concatenated in problem order: q, level and view_cos (mode 1: mTrackViewCos
+ * of the live rows, 0 for inert ones; may be NULL) hold sum(npts) entries,
+ * n_in_view[p] = live rows of problem p (nToMatch).  nprob == 0 and
+ * npts[p] == 0 are valid.  ORBX_ERR_ARG for a bad mode / count / camera, a
+ * NULL array the mode reads, and where any problem counts a non-finite point;
+ * no output is written then. */
+int orbm_project_points(int mode, int nprob, const orbx_proj_camera* cameras,
+                        const orbx_proj_points* points, const int* npts,
+                        const orbx_proj_params* params, int device, orbx_query_proj* q,
+                        int32_t* level, float* view_cos, int* n_in_view);
+
+/* The same on device pointers, as methods of orbm_proj_plan (which stages the
+ * problem table and keeps the threshold tables): `camera` holds values, every
+ * pointer of `points` and every output is DEVICE memory.
+ * orbm_proj_plan_project: q[npts] and level[npts] are required, view_cos,
+ *   n_in_view and n_nonfinite (one int each) may be NULL; frame, qdesc, match
+ *   and nmatches are not read.
+ * orbm_proj_plan_track: projection followed by orbm_proj_plan_search's search
+ *   on the same stream with nq = npts and qdesc = the map points' descriptors
+ *   [npts][32]; match[frame.n] holds map-point indices.  q and level may be
+ *   NULL (the rows then stay in the plan's scratch).  npts <= max_nq and
+ *   frame.n <= max_n of the plan.
+ * Asynchronous on `stream`; n_nonfinite is left for the caller to read.  The
+ * one-host-thread and cross-stream rules of orbm_proj_plan_search hold. */
+typedef struct {
+  orbx_proj_camera camera;
+  orbx_proj_points points;
+  int npts;
+  orbx_query_proj* q;
+  int32_t* level;
+  float* view_cos;
+  int* n_in_view;
+  int* n_nonfinite;
+  orbx_proj_frame frame; /* track only, as in orbx_proj_problem */
+  const uint8_t* qdesc;
+  int32_t* match;
+  int* nmatches;
+} orbx_proj_build_problem;
+int orbm_proj_plan_project(orbm_proj_plan* plan, int mode, int nprob,
+                           const orbx_proj_build_problem* problems,
+                           const orbx_proj_params* params, void* stream);
+int orbm_proj_plan_track(orbm_proj_plan* plan, int mode, int nprob,
+                         const orbx_proj_build_problem* problems,
+                         const orbx_proj_params* params, float nnratio, int th_dist,
+                         int check_ori, void* stream);
 
 /* ---------------------------------------------------------------------------
  * SURVEY.md §8f rank 4.

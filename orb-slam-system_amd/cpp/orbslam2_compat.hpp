@@ -22,7 +22,11 @@
 //     (GetMapPointMatches, GetMapPoint, isBad, mvKeysUn, mFeatVec,
 //     mDescriptors, mvLevelSigma2, N; for Fuse / SearchBySim3 also the pose
 //     getters, fx .. cy, IsInImage, mvScaleFactors, the grid constants and
-//     the MapPoint members of src/ORBmatcher.cc:504-730).
+//     the MapPoint members of src/ORBmatcher.cc:504-730), and the last-frame
+//     and keyframe forms of SearchByProjection (:34-39) with a
+//     SearchLocalPoints helper for Tracking's frustum loop, projected and
+//     searched on the device (these read mTcw, mOw, the intrinsics, the image
+//     bounds, the scale tables and, beyond the reference, MapPoint::GetMaxDistance()).
 // A project that has OpenCV keeps its cv:: and uses INTEGRATION.md's glue
 // instead; define ORBX_COMPAT_NO_CV to take cv:: from OpenCV headers.
 #ifndef ORBX_ORBSLAM2_COMPAT_HPP
@@ -728,7 +732,184 @@ class ORBmatcher {
     return n;
   }
 
+  // The frustum test of Tracking::SearchLocalPoints for a whole vector of map
+  // points in one device call (Frame::isInFrustum per point in the reference,
+  // src/Frame.cc:249-305): writes mbTrackInView, mTrackProjX / Y / XR,
+  // mnTrackScaleLevel and mTrackViewCos back and returns nToMatch.  Points
+  // with mnLastFrameSeen == F.mnId and bad points are skipped as there (their
+  // mbTrackInView is left alone for the former, as Tracking.cc does).  MP
+  // needs one accessor the reference lacks: GetMaxDistance(), the raw
+  // mfMaxDistance that PredictScale divides.
+  template <class FR, class MP>
+  int SearchLocalPoints(FR& F, const std::vector<MP*>& vpMapPoints, float viewingCosLimit = 0.5f) {
+    const int n = (int)vpMapPoints.size();
+    ProjInputs I(n);
+    for (int i = 0; i < n; ++i) {
+      MP* pMP = vpMapPoints[i];
+      I.skip[i] = !pMP || pMP->mnLastFrameSeen == F.mnId || pMP->isBad();
+      if (I.skip[i]) continue;
+      pMP->mbTrackInView = false;
+      I.set_pos(i, pMP->GetWorldPos());
+      const cv::Mat N = pMP->GetNormal();
+      for (int k = 0; k < 3; ++k) I.normal[3 * i + k] = N.template at<float>(k);
+      I.dmin[i] = pMP->GetMinDistanceInvariance();
+      I.dmax[i] = pMP->GetMaxDistanceInvariance();
+      I.draw[i] = pMP->GetMaxDistance();
+    }
+    const orbx_proj_camera cam = proj_camera(F, F.mOw);
+    const orbx_proj_params prm = {1.0f, viewingCosLimit, ORBX_LEVEL_RULE_NEITHER};
+    int nToMatch = 0;
+    I.project(1, cam, prm, &nToMatch, "SearchLocalPoints");
+    for (int i = 0; i < n; ++i) {
+      if (I.level[i] < 0) continue;
+      MP* pMP = vpMapPoints[i];
+      pMP->mbTrackInView = true;
+      pMP->mTrackProjX = I.q[i].x;
+      pMP->mTrackProjY = I.q[i].y;
+      pMP->mTrackProjXR = I.q[i].xr;
+      pMP->mnTrackScaleLevel = I.level[i];
+      pMP->mTrackViewCos = I.vcos[i];
+    }
+    return nToMatch;
+  }
+
+  // SearchByProjection(Frame& Current, const Frame& Last, th, bMono)
+  // (:732-818): projection and search on the device; row i is
+  // LastFrame.mvpMapPoints[i].
+  template <class FR>
+  int SearchByProjection(FR& CurrentFrame, const FR& LastFrame, const float th, const bool bMono) {
+    const auto Rcw = CurrentFrame.mTcw.rowRange(0, 3).colRange(0, 3);
+    const auto tcw = CurrentFrame.mTcw.rowRange(0, 3).col(3);
+    const auto twc = -Rcw.t() * tcw;
+    const auto Rlw = LastFrame.mTcw.rowRange(0, 3).colRange(0, 3);
+    const auto tlw = LastFrame.mTcw.rowRange(0, 3).col(3);
+    const auto tlc = Rlw * twc + tlw;
+    const bool bForward = tlc.template at<float>(2) > CurrentFrame.mb && !bMono;
+    const bool bBackward = -tlc.template at<float>(2) > CurrentFrame.mb && !bMono;
+    const int n = LastFrame.N;
+    ProjInputs I(n);
+    for (int i = 0; i < n; ++i) {
+      auto* pMP = LastFrame.mvpMapPoints[i];
+      I.skip[i] = !pMP || LastFrame.mvbOutlier[i];
+      if (I.skip[i]) continue;
+      I.set_pos(i, pMP->GetWorldPos());
+      I.set_desc(i, pMP->GetDescriptor());
+      I.octave[i] = LastFrame.mvKeys[i].octave;
+      I.angle[i] = LastFrame.mvKeys[i].angle;
+    }
+    const orbx_proj_camera cam = proj_camera(CurrentFrame, twc);
+    const orbx_proj_params prm = {th, 0.0f, bForward ? ORBX_LEVEL_RULE_FORWARD
+                                            : bBackward ? ORBX_LEVEL_RULE_BACKWARD : ORBX_LEVEL_RULE_NEITHER};
+    int nLive = 0;
+    I.project(2, cam, prm, &nLive, "SearchByProjection");
+    return I.search(2, CurrentFrame, LastFrame.mvpMapPoints, mfNNratio, TH_HIGH, mbCheckOrientation);
+  }
+
+  // SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&, th, ORBdist)
+  // (:820-894); row i is pKF->GetMapPointMatches()[i].
+  template <class FR, class KF, class MP>
+  int SearchByProjection(FR& CurrentFrame, KF* pKF, const std::set<MP*>& sAlreadyFound, const float th,
+                         const int ORBdist) {
+    const auto Rcw = CurrentFrame.mTcw.rowRange(0, 3).colRange(0, 3);
+    const auto tcw = CurrentFrame.mTcw.rowRange(0, 3).col(3);
+    const auto Ow = -Rcw.t() * tcw;
+    const std::vector<MP*> vpMPs = pKF->GetMapPointMatches();
+    const int n = (int)vpMPs.size();
+    ProjInputs I(n);
+    for (int i = 0; i < n; ++i) {
+      MP* pMP = vpMPs[i];
+      I.skip[i] = !pMP || pMP->isBad() || sAlreadyFound.count(pMP);
+      if (I.skip[i]) continue;
+      I.set_pos(i, pMP->GetWorldPos());
+      I.set_desc(i, pMP->GetDescriptor());
+      I.draw[i] = pMP->GetMaxDistance();
+      I.angle[i] = pKF->mvKeys[i].angle;
+    }
+    const orbx_proj_camera cam = proj_camera(CurrentFrame, Ow);
+    const orbx_proj_params prm = {th, 0.0f, ORBX_LEVEL_RULE_NEITHER};
+    int nLive = 0;
+    I.project(3, cam, prm, &nLive, "SearchByProjection");
+    return I.search(3, CurrentFrame, vpMPs, mfNNratio, ORBdist, mbCheckOrientation);
+  }
+
  protected:
+  // orbx_proj_camera of a Frame; Ow = mOw (mode 1) or twc (modes 2, 3)
+  template <class FR, class M>
+  static orbx_proj_camera proj_camera(const FR& F, const M& Ow) {
+    orbx_proj_camera c;
+    memset(&c, 0, sizeof c);
+    for (int r = 0; r < 3; ++r) {
+      for (int k = 0; k < 3; ++k) c.Rcw[3 * r + k] = F.mTcw.template at<float>(r, k);
+      c.tcw[r] = F.mTcw.template at<float>(r, 3);
+      c.ow[r] = Ow.template at<float>(r);
+    }
+    c.fx = F.fx;
+    c.fy = F.fy;
+    c.cx = F.cx;
+    c.cy = F.cy;
+    c.mbf = F.mbf;
+    c.min_x = F.mnMinX;
+    c.max_x = F.mnMaxX;
+    c.min_y = F.mnMinY;
+    c.max_y = F.mnMaxY;
+    c.nlevels = F.mnScaleLevels;
+    if (c.nlevels < 1 || c.nlevels > ORBX_PROJ_MAX_LEVELS || (int)F.mvScaleFactors.size() < c.nlevels)
+      orbx_throw(ORBX_ERR_ARG, "projection camera");
+    for (int l = 0; l < c.nlevels; ++l) c.scale_factors[l] = F.mvScaleFactors[l];
+    c.log_scale_factor = F.mfLogScaleFactor;
+    return c;
+  }
+
+  // the point arrays of one orbm_project_points problem, its rows, and the
+  // search over them
+  struct ProjInputs {
+    int n;
+    std::vector<float> pos, normal, dmin, dmax, draw, angle, vcos;
+    std::vector<int32_t> octave, level;
+    std::vector<uint8_t> skip, qdesc;
+    std::vector<orbx_query_proj> q;
+    explicit ProjInputs(int n_)
+        : n(n_), pos(3 * (size_t)n_), normal(3 * (size_t)n_), dmin(n_), dmax(n_), draw(n_), angle(n_),
+          vcos(n_ ? n_ : 1), octave(n_), level(n_ ? n_ : 1, -1), skip(n_), qdesc(32 * (size_t)n_),
+          q(n_ ? n_ : 1) {}
+    template <class M>
+    void set_pos(int i, const M& P) {
+      for (int k = 0; k < 3; ++k) pos[3 * (size_t)i + k] = P.template at<float>(k);
+    }
+    template <class M>
+    void set_desc(int i, const M& d) { memcpy(&qdesc[32 * (size_t)i], d.ptr(0), 32); }
+    void project(int mode, const orbx_proj_camera& cam, const orbx_proj_params& prm, int* nlive, const char* what) {
+      const orbx_proj_points P = {pos.data(), normal.data(), dmin.data(), dmax.data(), draw.data(),
+                                  octave.data(), angle.data(), skip.data()};
+      orbx_throw(orbm_project_points(mode, 1, &cam, &P, &n, &prm, 0, q.data(), level.data(), vcos.data(), nlive),
+                 what);
+    }
+    // F.mvpMapPoints[idx] = who[row] for every feature a row took
+    template <class FR, class MPV>
+    int search(int mode, FR& F, const MPV& who, float nnratio, int th_dist, bool check_ori) {
+      std::vector<uint8_t> occ(F.N > 0 ? F.N : 0);
+      for (int i = 0; i < F.N; ++i) occ[i] = F.mvpMapPoints[i] != nullptr;
+      orbx_proj_frame pf;
+      pf.n = F.N;
+      pf.keys = reinterpret_cast<const orbx_keypoint*>(F.mvKeysUn.data());
+      pf.desc = F.mDescriptors.data;
+      pf.uright = nullptr;
+      pf.occupied = occ.data();
+      pf.min_x = F.mnMinX;
+      pf.min_y = F.mnMinY;
+      pf.grid_w_inv = F.mfGridElementWidthInv;
+      pf.grid_h_inv = F.mfGridElementHeightInv;
+      std::vector<int32_t> m(F.N > 0 ? F.N : 1, -1);
+      int nm = 0;
+      orbx_throw(orbm_search_by_projection(mode, &pf, q.data(), qdesc.data(), n, nnratio, th_dist,
+                                           check_ori ? 1 : 0, 0, m.data(), &nm),
+                 "SearchByProjection");
+      for (int i = 0; i < F.N; ++i)
+        if (m[i] >= 0) F.mvpMapPoints[i] = who[m[i]];
+      return nm;
+    }
+  };
+
   template <class FR>
   static orbx_kf_frame init_frame(FR& F) {
     orbx_kf_frame f;

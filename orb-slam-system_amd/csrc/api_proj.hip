@@ -8,6 +8,7 @@
 #include "../../include/orbx.h"
 #include "call_arena.h"
 #include "proj_internal.h"
+#include "proj_plan.h"
 
 namespace orbx {  // kernels_proj.hip
 __global__ void k_grid_build(const ProjProblem*);
@@ -17,7 +18,7 @@ __global__ void k_proj_resolve(const ProjProblem*, int, float, int, int);
 
 using namespace orbx;
 
-static ProjFrame proj_frame(const orbx_proj_frame* F) {
+ProjFrame orbx::proj_frame(const orbx_proj_frame* F) {
   ProjFrame PF;
   PF.n = F->n;
   PF.minX = F->min_x;
@@ -29,8 +30,8 @@ static ProjFrame proj_frame(const orbx_proj_frame* F) {
 
 // the three launches over nprob problems (device table d_probs): grid per
 // problem, candidates per (query, problem), the greedy walk per problem
-static void launch_proj(const ProjProblem* d_probs, int nprob, int max_n, int max_nq, int mode,
-                        float nnratio, int th_dist, int check_ori, hipStream_t s) {
+void orbx::launch_proj(const ProjProblem* d_probs, int nprob, int max_n, int max_nq, int mode,
+                       float nnratio, int th_dist, int check_ori, hipStream_t s) {
   int P = 1;
   while (P < max_n) P <<= 1;
   hipLaunchKernelGGL(k_grid_build, dim3((unsigned)nprob), dim3(1024), (size_t)P * 4, s, d_probs);
@@ -98,17 +99,7 @@ extern "C" int orbm_search_by_projection(int mode, const orbx_proj_frame* F,
 // Batched device form: many SearchByProjection problems (frames, each with
 // its query set) in one set of launches on device-resident inputs.
 // ---------------------------------------------------------------------------
-struct orbm_proj_plan {
-  int device = 0, max_prob = 0, max_n = 0, max_nq = 0;
-  DevBuf<ProjProblem> d_probs;
-  PinnedBuf<ProjProblem> h_probs;  // pinned staging of the problem table
-  Event ev;                        // the last table upload (h_probs reusable after it)
-  Event ev_done;                   // the last call's kernels (its grid / candidate scratch free after it)
-  DevBuf<int> d_cell_off, d_cell_feat;
-  DevBuf<uint32_t> d_cand;
-  DevBuf<int> d_ncand;
-  ~orbm_proj_plan() { hipSetDevice(device); }
-};
+// struct orbm_proj_plan: proj_plan.h (shared with api_projbuild.hip)
 
 extern "C" int orbm_proj_plan_create(int max_problems, int max_n, int max_nq, int device, orbm_proj_plan** out) {
   if (!out || max_problems < 1 || max_n < 1 || max_nq < 0) return ORBX_ERR_ARG;

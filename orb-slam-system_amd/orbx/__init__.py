@@ -64,6 +64,7 @@ EXPORTED = [
     "orbv_vocab_load_text", "orbv_vocab_create", "orbv_vocab_destroy", "orbv_vocab_info",
     "orbv_transform", "orbv_transform_batch", "orbv_check", "orbm_search_by_projection",
     "orbm_proj_plan_create", "orbm_proj_plan_destroy", "orbm_proj_plan_search",
+    "orbm_predict_scale_thresholds", "orbm_project_points", "orbm_proj_plan_project", "orbm_proj_plan_track",
     "orbm_compute_distinctive_descriptors", "orbx_undistort_keypoints", "orbx_selftest_sincos",
     "orbx_selftest_sincos_range", "orbm_search_for_triangulation", "orbm_keyframe_search",
     "orbm_search_for_initialization", "orbm_search_for_initialization_stats",
@@ -113,6 +114,35 @@ class ProjFrame(ctypes.Structure):
 class ProjProblem(ctypes.Structure):
     _fields_ = [("frame", ProjFrame), ("q", ctypes.c_void_p), ("qdesc", ctypes.c_void_p),
                 ("nq", ctypes.c_int), ("match", ctypes.c_void_p), ("nmatches", ctypes.c_void_p)]
+
+
+PROJ_MAX_LEVELS = 32  # ORBX_PROJ_MAX_LEVELS
+LEVEL_RULE_NEITHER, LEVEL_RULE_FORWARD, LEVEL_RULE_BACKWARD = 0, 1, 2
+
+
+class ProjCamera(ctypes.Structure):  # orbx_proj_camera
+    _fields_ = [("Rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("ow", ctypes.c_float * 3),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float),
+                ("cy", ctypes.c_float), ("mbf", ctypes.c_float),
+                ("min_x", ctypes.c_float), ("max_x", ctypes.c_float),
+                ("min_y", ctypes.c_float), ("max_y", ctypes.c_float), ("nlevels", ctypes.c_int),
+                ("scale_factors", ctypes.c_float * PROJ_MAX_LEVELS), ("log_scale_factor", ctypes.c_float)]
+
+
+class ProjPoints(ctypes.Structure):  # orbx_proj_points
+    _fields_ = [(n, ctypes.c_void_p) for n in ("pos", "normal", "min_dist_inv", "max_dist_inv", "max_dist",
+                                               "octave", "angle", "skip")]
+
+
+class ProjParams(ctypes.Structure):  # orbx_proj_params
+    _fields_ = [("th", ctypes.c_float), ("viewing_cos_limit", ctypes.c_float), ("level_rule", ctypes.c_int)]
+
+
+class ProjBuildProblem(ctypes.Structure):  # orbx_proj_build_problem
+    _fields_ = [("camera", ProjCamera), ("points", ProjPoints), ("npts", ctypes.c_int),
+                ("q", ctypes.c_void_p), ("level", ctypes.c_void_p), ("view_cos", ctypes.c_void_p),
+                ("n_in_view", ctypes.c_void_p), ("n_nonfinite", ctypes.c_void_p), ("frame", ProjFrame),
+                ("qdesc", ctypes.c_void_p), ("match", ctypes.c_void_p), ("nmatches", ctypes.c_void_p)]
 
 
 class BowFrame(ctypes.Structure):
@@ -236,6 +266,10 @@ _sig = {
     "orbm_proj_plan_create": (I, [I, I, I, I, P]),
     "orbm_proj_plan_destroy": (I, [P]),
     "orbm_proj_plan_search": (I, [P, I, I, P, F, I, I, P]),
+    "orbm_predict_scale_thresholds": (I, [F, I, P]),
+    "orbm_project_points": (I, [I, I, P, P, P, P, I, P, P, P, P]),
+    "orbm_proj_plan_project": (I, [P, I, I, P, P, P]),
+    "orbm_proj_plan_track": (I, [P, I, I, P, P, F, I, I, P]),
     "orbm_compute_distinctive_descriptors": (I, [P, P, I, I, P]),
     "orbx_undistort_keypoints": (I, [P, I, P, P, I, I, P]),
     "orbx_selftest_sincos": (I, [P, I, P, P]),
@@ -824,6 +858,124 @@ class ProjPlan:
         _check(_lib.orbm_proj_plan_search(self._h, mode, len(problems), ctypes.cast(arr, ctypes.c_void_p),
                                           float(nnratio), int(th_dist), 1 if check_ori else 0,
                                           _stream_handle(stream)), "orbm_proj_plan_search")
+
+
+    @staticmethod
+    def _build_problems(problems, track):
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+        arr = (ProjBuildProblem * max(len(problems), 1))()
+        for i, pb in enumerate(problems):
+            a = arr[i]
+            a.camera = proj_camera(pb["camera"])
+            pts = pb["points"]
+            a.points = ProjPoints(*[ptr(pts.get(n)) for n in POINT_FIELDS])
+            a.npts = pts["pos"].shape[0]
+            for n in ("q", "level", "view_cos", "n_in_view", "n_nonfinite"):
+                setattr(a, n, ptr(pb.get(n)))
+            if track:
+                fr = pb["frame"]
+                a.frame = ProjFrame(fr["keys"].shape[0], ptr(fr["keys"]), ptr(fr["desc"]), ptr(fr.get("uright")),
+                                    ptr(fr.get("occupied")), fr["min_x"], fr["min_y"], fr["grid_w_inv"],
+                                    fr["grid_h_inv"])
+                a.qdesc, a.match, a.nmatches = ptr(pb["qdesc"]), ptr(pb["match"]), ptr(pb["nmatches"])
+        return arr
+
+    def project(self, mode, problems, th=1.0, viewing_cos_limit=0.5, level_rule=LEVEL_RULE_NEITHER, stream=None):
+        """orbm_proj_plan_project: query rows from map points and a pose, on the
+        device.  problems: list of dicts -- camera (a proj_camera dict: host
+        values), points (dict of cuda tensors: pos [npts, 3] f32 and, as the
+        mode reads them, normal [npts, 3], min_dist_inv, max_dist_inv, max_dist
+        f32, octave i32, angle f32, skip u8 or absent), outputs q [npts, 28] u8
+        (PROJ_QUERY_DTYPE rows), level [npts] i32, and optionally view_cos
+        [npts] f32, n_in_view [1] i32, n_nonfinite [1] i32.  Asynchronous."""
+        arr = self._build_problems(problems, False)
+        prm = ProjParams(float(th), float(viewing_cos_limit), int(level_rule))
+        _check(_lib.orbm_proj_plan_project(self._h, mode, len(problems), ctypes.cast(arr, ctypes.c_void_p),
+                                           ctypes.byref(prm), _stream_handle(stream)), "orbm_proj_plan_project")
+
+    def track(self, mode, problems, th=1.0, viewing_cos_limit=0.5, level_rule=LEVEL_RULE_NEITHER, nnratio=0.6,
+              th_dist=100, check_ori=True, stream=None):
+        """orbm_proj_plan_track: project() followed by search() on the same
+        stream.  Each problem adds frame (dict as in search(): keys, desc,
+        uright, occupied, grid floats), qdesc [npts, 32] u8 (the map points'
+        descriptors) and the outputs match [n] i32 (map-point indices) and
+        nmatches [1] i32; q and level may be left out."""
+        arr = self._build_problems(problems, True)
+        prm = ProjParams(float(th), float(viewing_cos_limit), int(level_rule))
+        _check(_lib.orbm_proj_plan_track(self._h, mode, len(problems), ctypes.cast(arr, ctypes.c_void_p),
+                                         ctypes.byref(prm), float(nnratio), int(th_dist), 1 if check_ori else 0,
+                                         _stream_handle(stream)), "orbm_proj_plan_track")
+
+
+POINT_FIELDS = ("pos", "normal", "min_dist_inv", "max_dist_inv", "max_dist", "octave", "angle", "skip")
+_POINT_DTYPES = dict(pos=np.float32, normal=np.float32, min_dist_inv=np.float32, max_dist_inv=np.float32,
+                     max_dist=np.float32, octave=np.int32, angle=np.float32, skip=np.uint8)
+
+
+def proj_camera(cam):
+    """orbx_proj_camera from a dict: Rcw (3x3), tcw (3), ow (3), fx, fy, cx, cy,
+    mbf, min_x, max_x, min_y, max_y, scale_factors (nlevels), log_scale_factor."""
+    if isinstance(cam, ProjCamera):
+        return cam
+    sf = np.asarray(cam["scale_factors"], np.float32).reshape(-1)
+    if not 1 <= len(sf) <= PROJ_MAX_LEVELS:
+        raise OrbxError(ERR_ARG, "proj_camera: 1 .. %d scale factors expected" % PROJ_MAX_LEVELS)
+    c = ProjCamera()
+    c.Rcw[:] = np.asarray(cam["Rcw"], np.float32).reshape(9).tolist()
+    c.tcw[:] = np.asarray(cam["tcw"], np.float32).reshape(3).tolist()
+    c.ow[:] = np.asarray(cam["ow"], np.float32).reshape(3).tolist()
+    for n in ("fx", "fy", "cx", "cy", "mbf", "min_x", "max_x", "min_y", "max_y", "log_scale_factor"):
+        setattr(c, n, float(np.float32(cam[n])))
+    c.nlevels = len(sf)
+    c.scale_factors[:len(sf)] = sf.tolist()
+    return c
+
+
+def predict_scale_thresholds(log_scale_factor, nlevels):
+    """orbm_predict_scale_thresholds: float32[nlevels - 1], thr[L] = the smallest
+    positive ratio whose MapPoint::PredictScale level exceeds L."""
+    thr = np.zeros(max(int(nlevels) - 1, 1), np.float32)
+    _check(_lib.orbm_predict_scale_thresholds(float(np.float32(log_scale_factor)), int(nlevels), _p(thr)),
+           "orbm_predict_scale_thresholds")
+    return thr[:max(int(nlevels) - 1, 0)].copy()
+
+
+def project_points(mode, problems, th=1.0, viewing_cos_limit=0.5, level_rule=LEVEL_RULE_NEITHER, device=0):
+    """orbm_project_points on host arrays.  problems: list of (camera dict,
+    points dict of numpy arrays named as POINT_FIELDS).  Returns per problem
+    (q PROJ_QUERY_DTYPE[npts], level int32[npts], view_cos float32[npts] (mode
+    1, else None), n_in_view)."""
+    nprob = len(problems)
+    cams = (ProjCamera * max(nprob, 1))()
+    pts = (ProjPoints * max(nprob, 1))()
+    npts = np.zeros(max(nprob, 1), np.int32)
+    keep = []
+    for i, (cam, P) in enumerate(problems):
+        cams[i] = proj_camera(cam)
+        arrs = {}
+        for n in POINT_FIELDS:
+            if P.get(n) is not None:
+                arrs[n] = np.ascontiguousarray(P[n], _POINT_DTYPES[n])
+        keep.append(arrs)
+        pts[i] = ProjPoints(*[_p(arrs.get(n)) for n in POINT_FIELDS])
+        npts[i] = len(np.asarray(P["pos"]).reshape(-1, 3))
+    total = int(npts[:nprob].sum())
+    q = np.zeros(max(total, 1), PROJ_QUERY_DTYPE)
+    level = np.zeros(max(total, 1), np.int32)
+    vc = np.zeros(max(total, 1), np.float32) if mode == 1 else None
+    niv = np.zeros(max(nprob, 1), np.int32)
+    prm = ProjParams(float(th), float(viewing_cos_limit), int(level_rule))
+    _check(_lib.orbm_project_points(mode, nprob, ctypes.cast(cams, ctypes.c_void_p),
+                                    ctypes.cast(pts, ctypes.c_void_p), _p(npts), ctypes.byref(prm), device,
+                                    _p(q), _p(level), _p(vc), _p(niv)), "orbm_project_points")
+    out, off = [], 0
+    for i in range(nprob):
+        n = int(npts[i])
+        out.append((q[off:off + n].copy(), level[off:off + n].copy(),
+                    None if vc is None else vc[off:off + n].copy(), int(niv[i])))
+        off += n
+    return out
 
 
 def compute_distinctive_descriptors(groups, device=0):
