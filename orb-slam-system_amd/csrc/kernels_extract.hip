@@ -305,10 +305,17 @@ __global__ __launch_bounds__(256) void k_pyramid(const uint8_t* __restrict__ fra
         // re-store that row (same bytes), so the loop needs no exec masking
         const int nm1 = nrows - 1;
         int rv = r0, rw = __builtin_amdgcn_readfirstlane(r0);
+        // R in an SGPR for the trip counter (the compiler drops the builtin
+        // readfirstlane above as redundant and keeps R in a VGPR)
+        int Rs;
+        asm("v_readfirstlane_b32 %0, %1" : "=s"(Rs) : "v"(R));
         while (rw < nrows) {
           const uint32_t r = (uint32_t)min(rv, nm1);
           rv += R;
-          rw = __builtin_amdgcn_readfirstlane(rw + R);  // a separate scalar trip counter (opaque: not folded into rv)
+          // a separate scalar trip counter (opaque: not folded into rv), both
+          // operands in SGPRs: one s_add_i32 (v_add_u32 + v_readfirstlane_b32
+          // as readfirstlane(rw + R))
+          asm("s_add_i32 %0, %0, %1" : "+s"(rw) : "s"(Rs) : "scc");
           const uint2 e = *reinterpret_cast<const uint2*>(plds + (ylb + 8u * r));
           // SDWA halves of the entry: hbase + off0 / off1 here, b0 / b1 (e.y's
           // words) as operand selects of the vertical multiplies below

@@ -580,27 +580,25 @@ __device__ __forceinline__ void mfma_tile(const v4i_ (&af)[NS], const v4i_ (&bf)
 // 2^23 + 2h 2^PB + p: an integer below 2^24 (2h <= 2K <= 384 for NK 6 with
 // PB 14, <= 512 for NK 8 with PB 13), exact in f32, whose bit pattern
 // 0x4B000000 + h 2^(PB+1) + p orders like (h, p) -- the key itself, with
-// no per-key VALU (the plain form spends a shift and an add per key).  The
-// per-tile start values are the lane's 16 constants plus t0 (8 v_pk_add_f32).
+// no per-key VALU (the plain form spends a shift and an add per key).  Every
+// tile starts from the lane's 16 constants alone (p = the position inside the
+// tile), so its keys are tile-local; t0 is added, as an integer on the bit
+// pattern (linear in p while the value stays in [2^23, 2^24)), only to the
+// keys that go to an insertion.  (t0 in the start values: 8 v_pk_add_f32 per
+// tile directly ahead of the MFMA chain.)
 // Keys become (h << 16 | p) when the row's list is written out.
 #define MC_PB(NK) ((NK) == 6 ? 14 : 13)
 #define MC_KBASE 0x4B000000u
+// a key no list takes: above every sentinel, and + t0 (< 2^14) does not wrap
+#define MC_KNONE 0xFFFF0000u
 #ifndef MC_TOP3
 #define MC_TOP3 1 /* 1: per-lane top-3 of the tile's 16 keys, two insertions (A/B: 0 = one per key) */
 #endif
-typedef float v2f_ __attribute__((ext_vector_type(2)));
 
 template <int NS, int PB>
-__device__ __forceinline__ void mfma_tile_pk(const v4i_ (&af)[NS], const v4i_ (&bf)[NS], float t0f,
+__device__ __forceinline__ void mfma_tile_pk(const v4i_ (&af)[NS], const v4i_ (&bf)[NS], uint32_t t0,
                                              int n2, bool last, uint32_t (&L)[ORBM_T], const v16f_& cb) {
-  v16f_ ci;
-#pragma unroll
-  for (int i = 0; i < 16; i += 2) {
-    const v2f_ v = v2f_{cb[i], cb[i + 1]} + v2f_{t0f, t0f};
-    ci[i] = v[0];
-    ci[i + 1] = v[1];
-  }
-  v16f_ C = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fp4_slot(af[0]), fp4_slot(bf[0]), ci, 4, 4,
+  v16f_ C = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fp4_slot(af[0]), fp4_slot(bf[0]), cb, 4, 4,
                                                             0, 0x7F + PB, 0, 0x7F);
 #pragma unroll
   for (int s = 1; s < NS; ++s)
@@ -609,18 +607,19 @@ __device__ __forceinline__ void mfma_tile_pk(const v4i_ (&af)[NS], const v4i_ (&
   uint32_t k[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) k[i] = __float_as_uint(C[i]);
-  if (last) {  // wave-uniform: positions past the list
+  if (last) {  // wave-uniform: positions past the list (tile-local: n2 - t0 in 1..31)
+    const uint32_t nl = (uint32_t)n2 - t0;
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      if ((k[i] & ((1u << PB) - 1u)) >= (uint32_t)n2) k[i] = 0xFFFFFFFFu;
+      if ((k[i] & ((1u << PB) - 1u)) >= nl) k[i] = MC_KNONE;
   }
 #if MC_TOP3
   // the lane's three smallest keys (two running chains of med3 insertions,
   // then the lower half of the bitonic 6-sequence a1 a2 a3 b3 b2 b1); on
   // these frames most tiles hold a lane with one key under its list's last
   // entry, few a lane with three: two wave-level insertions replace up to 16
-  uint32_t a1 = min(k[0], k[1]), a2 = max(k[0], k[1]), a3 = 0xFFFFFFFFu;
-  uint32_t b1 = min(k[8], k[9]), b2 = max(k[8], k[9]), b3 = 0xFFFFFFFFu;
+  uint32_t a1 = min(k[0], k[1]), a2 = max(k[0], k[1]), a3 = MC_KNONE;
+  uint32_t b1 = min(k[8], k[9]), b2 = max(k[8], k[9]), b3 = MC_KNONE;
 #pragma unroll
   for (int i = 2; i < 8; ++i) {
     a3 = med3u(a2, k[i], a3);
@@ -633,39 +632,44 @@ __device__ __forceinline__ void mfma_tile_pk(const v4i_ (&af)[NS], const v4i_ (&
   const uint32_t l1 = min(a1, b3), l2 = min(a2, b2), l3 = min(a3, b1);
   const uint32_t m1 = min(min(l1, l2), l3), m3 = max(max(l1, l2), l3);
   const uint32_t m2 = med3u(l1, l2, l3);
-  if (__ballot(m1 < L[ORBM_T - 1])) {
-    topk_insert(L, m1);
-    if (__ballot(m2 < L[ORBM_T - 1])) {
-      topk_insert(L, m2);
-      if (__ballot(m3 < L[ORBM_T - 1])) {
+  // the list holds whole keys: + t0 on the three that can be inserted
+  const uint32_t g1 = m1 + t0;
+  if (__ballot(g1 < L[ORBM_T - 1])) {
+    topk_insert(L, g1);
+    const uint32_t g2 = m2 + t0;
+    if (__ballot(g2 < L[ORBM_T - 1])) {
+      topk_insert(L, g2);
+      if (__ballot(m3 + t0 < L[ORBM_T - 1])) {
         // some lane has a third key under its last entry: the remaining keys
         // (> m2; keys are unique in a lane) against the current threshold.
         // An insertion runs in every lane once any lane needs it, so keys a
         // lane already inserted (<= m2) become no-op keys first
-        const uint32_t l7 = L[ORBM_T - 1];
+        // The threshold in the tile's frame (the last entry is a key or
+        // the sentinel, both >= MC_KBASE > t0: the subtraction does not wrap)
+        const uint32_t l7 = L[ORBM_T - 1] - t0;
         unsigned long long bm[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          k[i] = k[i] > m2 ? k[i] : 0xFFFFFFFFu;
+          k[i] = k[i] > m2 ? k[i] : MC_KNONE;
           bm[i] = __ballot(k[i] < l7);
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-          if (bm[i]) topk_insert(L, k[i]);
+          if (bm[i]) topk_insert(L, k[i] + t0);
       }
     }
   }
 #else
   uint32_t m = min(min(min(k[0], k[1]), min(k[2], k[3])), min(min(k[4], k[5]), min(k[6], k[7])));
   m = min(m, min(min(min(k[8], k[9]), min(k[10], k[11])), min(min(k[12], k[13]), min(k[14], k[15]))));
-  if (__ballot(m < L[ORBM_T - 1])) {
-    const uint32_t l7 = L[ORBM_T - 1];
+  if (__ballot(m + t0 < L[ORBM_T - 1])) {
+    const uint32_t l7 = L[ORBM_T - 1] - t0;
     unsigned long long bm[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) bm[i] = __ballot(k[i] < l7);
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      if (bm[i]) topk_insert(L, k[i]);
+      if (bm[i]) topk_insert(L, k[i] + t0);
   }
 #endif
 }
@@ -747,13 +751,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
   v4i_ af[NS], an[NS];
 #if ORBM_FP4
   const v16f_ ci = fp4_acc_init<NS>();
-  // PK: element i's start value without t0: 2^23 + K 2^PB + 4h + (i & 3) + 8 (i >> 2)
+  // PK: element i's start value, the same for every tile: 2^23 + K 2^PB + 4h + (i & 3) + 8 (i >> 2)
   v16f_ cb;
 #pragma unroll
   for (int i = 0; i < 16; ++i)
     cb[i] = (float)(8388608 + (64 * NS << PB) + 4 * h + (i & 3) + 8 * (i >> 2));
 #define MC_TILE(F, T0) \
-  (PK ? mfma_tile_pk<NS, PB>(F, bf[t], (float)(T0), n2, (T0) + 32 > n2, L[t], cb) \
+  (PK ? mfma_tile_pk<NS, PB>(F, bf[t], (uint32_t)(T0), n2, (T0) + 32 > n2, L[t], cb) \
       : mfma_tile<NS>(F, bf[t], (uint32_t)(T0), n2, hoff, L[t], ci))
 #else
   const v16f_ ci = {};

@@ -9,8 +9,9 @@
  *
  * Strategy (identical on host and device):
  *   1. `orbx_sincos_core` evaluates sin/cos in double precision with only
- *      IEEE add/sub/mul (Cody-Waite pi/2 reduction + fdlibm kernel
- *      polynomials) and rounds to float.  Compiled with -ffp-contract=off on
+ *      IEEE add/sub/mul and an exact floor (Cody-Waite pi/2 reduction +
+ *      fdlibm kernel polynomials), rounds to float and applies the quadrant
+ *      as a swap and sign-bit flips.  Compiled with -ffp-contract=off on
  *      both gcc and hipcc, so host and device results are bit-identical.
  *   2. tools/gen_sincos_table.c enumerates EVERY float angle the extractor can
  *      produce (x in [0, f32(360*factorPI)]) against the host's glibc
@@ -39,9 +40,22 @@
 #define ORBX_INVPIO2  6.36619772367581382433e-01
 
 static ORBX_HD inline double orbx_floor_d(double v) {
-  /* exact floor without a library call (|v| < 2^52 here) */
-  double t = (double)(int64_t)v;
-  return (t > v) ? t - 1.0 : t;
+  /* exact IEEE floor: one v_floor_f64 on the device, floor() / roundsd on the
+   * host (a (double)(int64_t)v form costs ~15 VALU on gfx950, which has no
+   * f64 <-> i64 convert) */
+  return __builtin_floor(v);
+}
+
+static ORBX_HD inline uint32_t orbx_f2u(float f) {
+  union { float f; uint32_t u; } v;
+  v.f = f;
+  return v.u;
+}
+
+static ORBX_HD inline float orbx_u2f(uint32_t u) {
+  union { float f; uint32_t u; } v;
+  v.u = u;
+  return v.f;
 }
 
 static ORBX_HD inline double orbx_ksin(double r) {
@@ -69,27 +83,14 @@ static ORBX_HD inline void orbx_sincos_core(float x, float* s, float* c) {
   int k = (int)kd;
   double r = (xd - kd * ORBX_PIO2_1) - kd * ORBX_PIO2_1T;
   double sr = orbx_ksin(r), cr = orbx_kcos(r);
-  double sv, cv;
-  switch (k & 3) {
-    case 0: sv = sr; cv = cr; break;
-    case 1: sv = cr; cv = -sr; break;
-    case 2: sv = -sr; cv = -cr; break;
-    default: sv = -cr; cv = sr; break;
-  }
-  *s = (float)sv;
-  *c = (float)cv;
-}
-
-static ORBX_HD inline uint32_t orbx_f2u(float f) {
-  union { float f; uint32_t u; } v;
-  v.f = f;
-  return v.u;
-}
-
-static ORBX_HD inline float orbx_u2f(uint32_t u) {
-  union { float f; uint32_t u; } v;
-  v.u = u;
-  return v.f;
+  /* quadrant k & 3: (s, c) = (sr, cr), (cr, -sr), (-sr, -cr), (-cr, sr).
+   * Negation and selection commute with rounding, so round first, then swap
+   * on k & 1 and flip the float sign bits: sin in quadrants 2 and 3, cos in
+   * 1 and 2 -- no branches */
+  const uint32_t su = orbx_f2u((float)sr), cu = orbx_f2u((float)cr);
+  const uint32_t odd = (uint32_t)k & 1u;
+  *s = orbx_u2f((odd ? cu : su) ^ (((uint32_t)k & 2u) << 30));
+  *c = orbx_u2f((odd ? su : cu) ^ ((((uint32_t)k + 1u) & 2u) << 30));
 }
 
 #endif /* ORBX_SINCOS_H */
