@@ -35,7 +35,9 @@ extern "C" {
  * orbv_db_* keyframe database with its batched queries
  * (orbv_db_query_batch / orbv_db_query_batch_device), and the device-side projection
  * (orbx_proj_camera / orbx_proj_points / orbx_proj_params / orbx_proj_build_problem,
- * orbm_predict_scale_thresholds, orbm_project_points, orbm_proj_plan_project / _track), are
+ * orbm_predict_scale_thresholds, orbm_project_points, orbm_proj_plan_project / _track), and
+ * the keyframe form of it (orbx_kf_camera / orbx_kf_points / orbx_kf_problem,
+ * orbm_keyframe_project and the orbm_kf_plan_* entry points), are
  * additive (no existing struct or entry point changes), so the version stays 2. */
 #define ORBX_ABI_VERSION 2
 
@@ -824,6 +826,108 @@ int orbm_proj_plan_track(orbm_proj_plan* plan, int mode, int nprob,
                          const orbx_proj_build_problem* problems,
                          const orbx_proj_params* params, float nnratio, int th_dist,
                          int check_ori, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Device-side projection for ORBmatcher::Fuse (both forms) and SearchBySim3:
+ * map points and a pose in, orbx_kf_query rows out, and the
+ * device-pointer plan form of orbm_keyframe_search's search.
+ *   ORBX_KF_FORM_FUSE: p3Dc = Rcw * p + tcw; dist = |p - ow|; fx fy cx cy of
+ *           the target keyframe (src/ORBmatcher.cc:514-531, :582-599; for the
+ *           Scw form Rcw / tcw are rows 0..2 of Scw as they stand)
+ *   ORBX_KF_FORM_SIM3: p3Dc2 = sR21 * (Rcw * p + tcw) + t21 with Rcw / tcw =
+ *           R1w / t1w of pKF1; dist = |p3Dc2|; fx fy cx cy of pKF1, bounds
+ *           and scale tables of pKF2 (:639-642, :676-694); ow is not read
+ * Then, for both: Z < 0 rejects; invz = 1 / Z; x = X * invz; u = fma(x, fx,
+ * cx) (fused, as the reference's object has it); KeyFrame::IsInImage (u >=
+ * min_x && u < max_x && v >= min_y && v < max_y); dist outside [min_dist_inv,
+ * max_dist_inv] rejects; level = PredictScale(dist); radius = th *
+ * scale_factors[level].
+ * Point i writes query row i and level[i]; there is no compaction.  Where the
+ * reference executes `continue`, the row is inert: x = y = 0, radius = -1,
+ * level = -1, desc = the row's own pool index, and level[i] = -1.  The search's
+ * strict box test rejects every feature for it, so an inert row returns
+ * -1 / INT_MAX; queries never interact, so it changes no other row.
+ * The one deviation: a live row whose radius is not finite is written inert
+ * and counted in n_nonfinite.
+ * ------------------------------------------------------------------------- */
+enum { ORBX_KF_FORM_FUSE = 1, ORBX_KF_FORM_SIM3 = 2 };
+typedef struct {
+  float Rcw[9], tcw[3];        /* rotation (row-major) and translation: pKF (FUSE), pKF1 (SIM3) */
+  float ow[3];                 /* FUSE: camera centre, computed by the caller                */
+  float sR21[9], t21[3];       /* SIM3: (1 / s12) * R12^T and -sR21 * t12, by the caller     */
+  float fx, fy, cx, cy;
+  float min_x, max_x, min_y, max_y; /* mnMinX, mnMaxX, mnMinY, mnMaxY of the searched keyframe */
+  int nlevels;                 /* mnScaleLevels, 1 .. ORBX_PROJ_MAX_LEVELS                   */
+  float scale_factors[ORBX_PROJ_MAX_LEVELS]; /* mvScaleFactors, nlevels used                 */
+  float log_scale_factor;      /* mfLogScaleFactor: finite, > 0                              */
+} orbx_kf_camera;
+
+/* map points of one problem, npts entries per array */
+typedef struct {
+  const float* pos;           /* [npts][3] GetWorldPos()                                     */
+  const float* min_dist_inv;  /* GetMinDistanceInvariance()                                  */
+  const float* max_dist_inv;  /* GetMaxDistanceInvariance()                                  */
+  const float* max_dist;      /* the raw mfMaxDistance PredictScale divides                  */
+  const uint8_t* skip;        /* NULL = none; 1 where the reference skips the point before it
+                                 projects -- Fuse: null, bad, IsInKeyFrame / GetMapPoint(
+                                 GetIndexInKeyFrame); SearchBySim3: null, already matched, bad */
+} orbx_kf_points;
+
+/* nprob problems (problem p: cameras[p], points[p], npts[p]; th is shared) in
+ * one launch.  Host pointers; synchronous.  q and level hold sum(npts) entries
+ * in problem order, n_live[p] = the live rows of problem p.  q[..].desc =
+ * desc_base[p] + i (i when desc_base is NULL), so the rows go straight into
+ * orbm_keyframe_search with qoff = the prefix of npts, over a descriptor pool
+ * that is shared (every desc_base[p] = 0: one point set, many keyframes) or
+ * per problem (desc_base = that prefix).  nprob == 0 and npts[p] == 0 are
+ * valid.  ORBX_ERR_ARG for a bad form / count / camera, a negative desc_base,
+ * a NULL array, and where any problem counts a non-finite radius; no output
+ * is written then. */
+int orbm_keyframe_project(int form, int nprob, const orbx_kf_camera* cameras,
+                          const orbx_kf_points* points, const int* npts, const int32_t* desc_base,
+                          float th, int device, orbx_kf_query* q, int32_t* level, int* n_live);
+
+/* The same, and orbm_keyframe_search's search, on device pointers and
+ * asynchronous on `stream`.  A plan holds the scratch (grids, feature records,
+ * staged problem tables, query rows, PredictScale threshold tables) for
+ * max_problems problems of at most max_n features (<= 8192) and max_queries
+ * points; everything is allocated by _create.  One host thread calls a plan at
+ * a time; a call waits on the host for the previous call's table upload only,
+ * and its stream waits on the device for the previous call's kernels before it
+ * reuses the scratch.
+ * One problem: `camera` holds values; every pointer is DEVICE memory.  Point
+ * arrays and qdesc of different problems may alias (one point set, many
+ * keyframes).  Row i's descriptor is qdesc + 32 * q[i].desc; the rows the
+ * projection writes have desc = i.
+ * orbm_kf_plan_search: q[npts] is given (x, y, radius, level, desc in
+ *   [0, npts); a desc outside it returns -1 / INT_MAX); best_idx[npts] and
+ *   best_dist[npts] are written as orbm_keyframe_search writes them.  camera,
+ *   points, level, n_live and n_nonfinite are not read.
+ * orbm_kf_plan_project: q[npts] and level[npts] are written; n_live and
+ *   n_nonfinite (one int each) may be NULL; frame, qdesc, best_* are not read.
+ * orbm_kf_plan_project_search: both on one stream; q and level may be NULL
+ *   (the rows then stay in the plan's scratch). */
+typedef struct {
+  orbx_kf_camera camera;
+  orbx_kf_points points;
+  int npts;
+  const uint8_t* qdesc;  /* [npts][32] */
+  orbx_kf_frame frame;   /* keys: orbx_keypoint rows on the device */
+  orbx_kf_query* q;
+  int32_t* level;
+  int* n_live;
+  int* n_nonfinite;
+  int32_t* best_idx;
+  int32_t* best_dist;
+} orbx_kf_problem;
+typedef struct orbm_kf_plan orbm_kf_plan;
+int orbm_kf_plan_create(int max_problems, int max_n, int max_queries, int device, orbm_kf_plan** out);
+int orbm_kf_plan_destroy(orbm_kf_plan* plan);
+int orbm_kf_plan_search(orbm_kf_plan* plan, int nprob, const orbx_kf_problem* problems, void* stream);
+int orbm_kf_plan_project(orbm_kf_plan* plan, int form, int nprob, const orbx_kf_problem* problems,
+                         float th, void* stream);
+int orbm_kf_plan_project_search(orbm_kf_plan* plan, int form, int nprob,
+                                const orbx_kf_problem* problems, float th, void* stream);
 
 /* ---------------------------------------------------------------------------
  * SURVEY.md §8f rank 4.

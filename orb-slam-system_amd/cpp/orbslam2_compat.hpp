@@ -516,6 +516,19 @@ class ORBmatcher {
     return total;
   }
 
+  // Where the queries of Fuse (both forms, and the batched form) and of
+  // SearchBySim3 are built.  Host (the default): the reference's own cv::Mat
+  // statements, one map point at a time, in this header.  Device: one
+  // orbm_keyframe_project call over the map points' arrays; the
+  // rows then go to orbm_keyframe_search as they are, inert where the reference
+  // `continue`s, and the walk and its bookkeeping are the same.  u and v follow
+  // the reference's object there (one fused multiply-add), which a build of
+  // this header without contraction differs from in the last place.  MP then
+  // needs GetMaxDistance() (the raw mfMaxDistance that PredictScale divides),
+  // as a member or as a free function found by argument-dependent lookup.
+  enum class KfProjection { Host, Device };
+  void SetKfProjection(KfProjection m) { mKfProjection = m; }
+
   // Fuse(KeyFrame*, const vector<MapPoint*>&, th) (:504-568).  Three steps:
   // the queries are built with the reference's own statements, one
   // orbm_keyframe_search call finds every query's best feature, and the map
@@ -547,20 +560,35 @@ class ORBmatcher {
   int Fuse(const std::vector<KF*>& vpTargetKFs, const std::vector<MP*>& vpMapPoints, const float th = 3.0) {
     KfSearch S;
     std::vector<int32_t> slot(vpTargetKFs.size() * vpMapPoints.size(), -1);
-    for (size_t p = 0; p < vpTargetKFs.size(); ++p) {
-      KF* pKF = vpTargetKFs[p];
-      cv::Mat Rcw = pKF->GetRotation();
-      cv::Mat tcw = pKF->GetTranslation();
-      cv::Mat Ow = pKF->GetCameraCenter();
-      S.begin(pKF);
-      for (size_t i = 0; i < vpMapPoints.size(); ++i) {
-        MP* pMP = vpMapPoints[i];
-        if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
-        slot[p * vpMapPoints.size() + i] = fuse_query(S, pKF, Rcw, tcw, Ow, pMP, th);
+    if (mKfProjection == KfProjection::Device) {
+      // one shared point set (row i = vpMapPoints[i], desc_base = 0), a skip array per keyframe
+      KfPoints I(vpMapPoints);
+      for (size_t p = 0; p < vpTargetKFs.size(); ++p) {
+        KF* pKF = vpTargetKFs[p];
+        std::vector<uint8_t>& skip = I.begin(S, pKF, kf_camera(pKF, pKF, pKF->GetRotation(), pKF->GetTranslation(),
+                                                               pKF->GetCameraCenter()));
+        for (size_t i = 0; i < vpMapPoints.size(); ++i) {
+          MP* pMP = vpMapPoints[i];
+          skip[i] = !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF);
+        }
       }
-      S.end();
+      I.run(S, ORBX_KF_FORM_FUSE, th, slot, "Fuse");
+    } else {
+      for (size_t p = 0; p < vpTargetKFs.size(); ++p) {
+        KF* pKF = vpTargetKFs[p];
+        cv::Mat Rcw = pKF->GetRotation();
+        cv::Mat tcw = pKF->GetTranslation();
+        cv::Mat Ow = pKF->GetCameraCenter();
+        S.begin(pKF);
+        for (size_t i = 0; i < vpMapPoints.size(); ++i) {
+          MP* pMP = vpMapPoints[i];
+          if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+          slot[p * vpMapPoints.size() + i] = fuse_query(S, pKF, Rcw, tcw, Ow, pMP, th);
+        }
+        S.end();
+      }
+      S.run("Fuse");
     }
-    S.run("Fuse");
     int nFused = 0;
     for (size_t p = 0; p < vpTargetKFs.size(); ++p) {
       KF* pKF = vpTargetKFs[p];
@@ -600,14 +628,24 @@ class ORBmatcher {
     M Ow = -Rcw.t() * tcw;
     KfSearch S;
     std::vector<int32_t> slot(vpPoints.size(), -1);
-    S.begin(pKF);
-    for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
-      MP* pMP = vpPoints[iMP];
-      if (!pMP || pMP->isBad() || pKF->GetMapPoint(pMP->GetIndexInKeyFrame(pKF))) continue;
-      slot[iMP] = fuse_query(S, pKF, Rcw, tcw, Ow, pMP, th);
+    if (mKfProjection == KfProjection::Device) {
+      KfPoints I(vpPoints);
+      std::vector<uint8_t>& skip = I.begin(S, pKF, kf_camera(pKF, pKF, Rcw, tcw, Ow));
+      for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
+        MP* pMP = vpPoints[iMP];
+        skip[iMP] = !pMP || pMP->isBad() || pKF->GetMapPoint(pMP->GetIndexInKeyFrame(pKF));
+      }
+      I.run(S, ORBX_KF_FORM_FUSE, th, slot, "Fuse");
+    } else {
+      S.begin(pKF);
+      for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
+        MP* pMP = vpPoints[iMP];
+        if (!pMP || pMP->isBad() || pKF->GetMapPoint(pMP->GetIndexInKeyFrame(pKF))) continue;
+        slot[iMP] = fuse_query(S, pKF, Rcw, tcw, Ow, pMP, th);
+      }
+      S.end();
+      S.run("Fuse");
     }
-    S.end();
-    S.run("Fuse");
     int nFused = 0;
     for (size_t iMP = 0; iMP < vpPoints.size(); iMP++) {
       MP* pMP = vpPoints[iMP];
@@ -657,28 +695,45 @@ class ORBmatcher {
     }
     KfSearch S;
     std::vector<int32_t> slot(vpMapPoints1.size(), -1);
-    S.begin(pKF2);
-    for (size_t i1 = 0; i1 < vpMapPoints1.size(); ++i1) {
-      MP* pMP1 = vpMapPoints1[i1];
-      if (!pMP1 || vbAlreadyMatched1[i1] || pMP1->isBad()) continue;
-      M p3Dw = pMP1->GetWorldPos();
-      M p3Dc1 = R1w * p3Dw + t1w;
-      M p3Dc2 = sR21 * p3Dc1 + t21;
-      if (p3Dc2.template at<float>(2) < 0.0f) continue;
-      float invz = 1.0f / p3Dc2.template at<float>(2);
-      float x = p3Dc2.template at<float>(0) * invz;
-      float y = p3Dc2.template at<float>(1) * invz;
-      float u = fx * x + cx;
-      float v = fy * y + cy;
-      if (!pKF2->IsInImage(u, v)) continue;
-      float dist = cv::norm(p3Dc2);
-      if (dist < pMP1->GetMinDistanceInvariance() || dist > pMP1->GetMaxDistanceInvariance()) continue;
-      int predictedLevel = pMP1->PredictScale(dist, pKF2);
-      float radius = th * pKF2->mvScaleFactors[predictedLevel];
-      slot[i1] = S.add(pMP1, u, v, radius, predictedLevel);
+    if (mKfProjection == KfProjection::Device) {
+      // intrinsics of pKF1, bounds and scale tables of pKF2, as the reference reads them
+      orbx_kf_camera cam = kf_camera(pKF1, pKF2, R1w, t1w, t1w);
+      for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) cam.sR21[3 * r + k] = sR21.template at<float>(r, k);
+        cam.t21[r] = t21.template at<float>(r);
+        cam.ow[r] = 0.0f;
+      }
+      KfPoints I(vpMapPoints1);
+      std::vector<uint8_t>& skip = I.begin(S, pKF2, cam);
+      for (size_t i1 = 0; i1 < vpMapPoints1.size(); ++i1) {
+        MP* pMP1 = vpMapPoints1[i1];
+        skip[i1] = !pMP1 || vbAlreadyMatched1[i1] || pMP1->isBad();
+      }
+      I.run(S, ORBX_KF_FORM_SIM3, th, slot, "SearchBySim3");
+    } else {
+      S.begin(pKF2);
+      for (size_t i1 = 0; i1 < vpMapPoints1.size(); ++i1) {
+        MP* pMP1 = vpMapPoints1[i1];
+        if (!pMP1 || vbAlreadyMatched1[i1] || pMP1->isBad()) continue;
+        M p3Dw = pMP1->GetWorldPos();
+        M p3Dc1 = R1w * p3Dw + t1w;
+        M p3Dc2 = sR21 * p3Dc1 + t21;
+        if (p3Dc2.template at<float>(2) < 0.0f) continue;
+        float invz = 1.0f / p3Dc2.template at<float>(2);
+        float x = p3Dc2.template at<float>(0) * invz;
+        float y = p3Dc2.template at<float>(1) * invz;
+        float u = fx * x + cx;
+        float v = fy * y + cy;
+        if (!pKF2->IsInImage(u, v)) continue;
+        float dist = cv::norm(p3Dc2);
+        if (dist < pMP1->GetMinDistanceInvariance() || dist > pMP1->GetMaxDistanceInvariance()) continue;
+        int predictedLevel = pMP1->PredictScale(dist, pKF2);
+        float radius = th * pKF2->mvScaleFactors[predictedLevel];
+        slot[i1] = S.add(pMP1, u, v, radius, predictedLevel);
+      }
+      S.end();
+      S.run("SearchBySim3");
     }
-    S.end();
-    S.run("SearchBySim3");
     int nMatches = 0;
     for (size_t i1 = 0; i1 < vpMapPoints1.size(); ++i1) {
       if (slot[i1] < 0) continue;
@@ -984,6 +1039,109 @@ class ORBmatcher {
     }
   };
 
+  // MapPoint::GetMaxDistance(): a member, else a free function found by
+  // argument-dependent lookup; a map point type with neither cannot take the
+  // device route
+  struct Rank0 {};
+  struct Rank1 : Rank0 {};
+  struct Rank2 : Rank1 {};
+  template <class MP>
+  static auto max_distance(MP* p, Rank2) -> decltype((float)p->GetMaxDistance()) {
+    return p->GetMaxDistance();
+  }
+  template <class MP>
+  static auto max_distance(MP* p, Rank1) -> decltype((float)GetMaxDistance(p)) {
+    return GetMaxDistance(p);
+  }
+  template <class MP>
+  static float max_distance(MP*, Rank0) {
+    orbx_throw(ORBX_ERR_UNSUPPORTED, "KfProjection::Device needs MapPoint::GetMaxDistance()");
+    return 0.0f;
+  }
+
+  // orbx_kf_camera: intrinsics of pKFi, bounds and scale tables of pKFs (the
+  // searched keyframe), the pose from the caller's matrices
+  template <class KF, class M1, class M2, class M3>
+  static orbx_kf_camera kf_camera(KF* pKFi, KF* pKFs, const M1& Rcw, const M2& tcw, const M3& Ow) {
+    orbx_kf_camera c;
+    memset(&c, 0, sizeof c);
+    const cv::Mat R = Rcw, t = tcw, O = Ow;
+    for (int r = 0; r < 3; ++r) {
+      for (int k = 0; k < 3; ++k) c.Rcw[3 * r + k] = R.template at<float>(r, k);
+      c.tcw[r] = t.template at<float>(r);
+      c.ow[r] = O.template at<float>(r);
+    }
+    c.fx = pKFi->fx;
+    c.fy = pKFi->fy;
+    c.cx = pKFi->cx;
+    c.cy = pKFi->cy;
+    c.min_x = pKFs->mnMinX;
+    c.max_x = pKFs->mnMaxX;
+    c.min_y = pKFs->mnMinY;
+    c.max_y = pKFs->mnMaxY;
+    c.nlevels = pKFs->mnScaleLevels;
+    if (c.nlevels < 1 || c.nlevels > ORBX_PROJ_MAX_LEVELS || (int)pKFs->mvScaleFactors.size() < c.nlevels)
+      orbx_throw(ORBX_ERR_ARG, "keyframe projection camera");
+    for (int l = 0; l < c.nlevels; ++l) c.scale_factors[l] = pKFs->mvScaleFactors[l];
+    c.log_scale_factor = pKFs->mfLogScaleFactor;
+    return c;
+  }
+
+  // the device route's inputs: one point set (row i = the list's entry i, its
+  // descriptor pool row i) shared by every problem, and per problem a camera
+  // and a skip array.  run() projects, hands the rows to KfSearch unchanged and
+  // fills slot[p * n + i] = the query's index, -1 for an inert row
+  struct KfPoints {
+    int n;
+    std::vector<float> pos, dmin, dmax, draw;
+    std::vector<uint8_t> pool;
+    std::vector<orbx_kf_camera> cams;
+    std::vector<std::vector<uint8_t> > skips;
+    template <class MP>
+    explicit KfPoints(const std::vector<MP*>& v)
+        : n((int)v.size()), pos(3 * v.size()), dmin(v.size()), dmax(v.size()), draw(v.size()),
+          pool(32 * v.size()) {
+      for (int i = 0; i < n; ++i) {
+        MP* pMP = v[i];
+        if (!pMP || pMP->isBad()) continue;  // skipped in every problem
+        const cv::Mat P = pMP->GetWorldPos();
+        for (int k = 0; k < 3; ++k) pos[3 * (size_t)i + k] = P.template at<float>(k);
+        dmin[i] = pMP->GetMinDistanceInvariance();
+        dmax[i] = pMP->GetMaxDistanceInvariance();
+        draw[i] = max_distance(pMP, Rank2());
+        const cv::Mat d = pMP->GetDescriptor();
+        memcpy(&pool[32 * (size_t)i], d.ptr(0), 32);
+      }
+    }
+    template <class KF>
+    std::vector<uint8_t>& begin(KfSearch& S, KF* kf, const orbx_kf_camera& cam) {
+      S.begin(kf);
+      cams.push_back(cam);
+      skips.push_back(std::vector<uint8_t>((size_t)n, 1));
+      return skips.back();
+    }
+    void run(KfSearch& S, int form, float th, std::vector<int32_t>& slot, const char* what) {
+      const size_t K = cams.size(), total = K * (size_t)n;
+      std::vector<orbx_kf_points> P(K);
+      std::vector<int> npts(K, n), nlive(K ? K : 1, 0);
+      std::vector<int32_t> base(K, 0), level(total ? total : 1, -1);
+      for (size_t p = 0; p < K; ++p) {
+        const orbx_kf_points one = {pos.data(), dmin.data(), dmax.data(), draw.data(), skips[p].data()};
+        P[p] = one;
+      }
+      S.q.assign(total ? total : 1, orbx_kf_query());
+      orbx_throw(orbm_keyframe_project(form, (int)K, cams.data(), P.data(), npts.data(), base.data(), th, 0,
+                                       S.q.data(), level.data(), nlive.data()),
+                 what);
+      S.q.resize(total);
+      S.qoff.assign(1, 0);
+      for (size_t p = 0; p < K; ++p) S.qoff.push_back((int32_t)((p + 1) * (size_t)n));
+      S.pool = pool;
+      for (size_t j = 0; j < total; ++j) slot[j] = level[j] >= 0 ? (int32_t)j : -1;
+      S.run(what);
+    }
+  };
+
   // the projection statements both Fuse forms share (:514-531, :582-599);
   // -1 where the reference `continue`s
   template <class KF, class MP, class M>
@@ -1082,6 +1240,7 @@ class ORBmatcher {
   float mfNNratio;
   bool mbCheckOrientation;
   BowKFFrame mBowKFFrame = BowKFFrame::Stub;
+  KfProjection mKfProjection = KfProjection::Host;
 };
 
 }  // namespace ORB_SLAM2

@@ -13,6 +13,10 @@
 //                   records KFW_G at a time: box test, octave gate, Hamming
 //                   distance, and the group minimum of distance << 16 | rank.
 //
+// k_kfwin_grid_kp and k_kfwin_search_plan are the same two bodies for
+// orbm_kf_plan (api_kfbuild.hip): the keys read as orbx_keypoint
+// rows, problems on blockIdx.y with their own queries, pool and results.
+//
 // The reference visits (ix, iy, position in the cell) and keeps the first
 // strict minimum; a record's position in the keyframe's order ("rank") grows
 // in exactly that order, so the first strict minimum is the smallest
@@ -22,6 +26,7 @@
 #include <stdint.h>
 
 #include "../../include/orbx.h"
+#include "kfbuild_internal.h"
 #include "kfwin_internal.h"
 #include "orbm_device.h"
 
@@ -33,10 +38,11 @@ __device__ __forceinline__ int kfw_f2i(float v) {
   return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)v : INT_MIN;
 }
 
-__global__ __launch_bounds__(1024) void k_kfwin_grid(const KfwProblem* __restrict__ probs) {
-  __shared__ uint32_t sk[KFW_MAXN];  // cell << 16 | index, 0xFFFFFFFF = in no cell
-  const KfwProblem PP = probs[blockIdx.x];
-  const KfwKey* __restrict__ keys = PP.key;
+// Key: the row type PP.key points at -- KfwKey as the host form uploads it, or
+// orbx_keypoint (28 bytes) where the caller's mvKeysUn is on the device
+template <class Key>
+__device__ __forceinline__ void kfwin_grid(const KfwProblem& PP, uint32_t* sk) {
+  const Key* __restrict__ keys = reinterpret_cast<const Key*>(PP.key);
   int* __restrict__ cell_off = PP.cell_off;
   if (!cell_off) return;  // a problem without queries: the whole block leaves
   int P = 1;
@@ -45,7 +51,7 @@ __global__ __launch_bounds__(1024) void k_kfwin_grid(const KfwProblem* __restric
   for (int i = tid; i < P; i += 1024) {
     uint32_t key = 0xFFFFFFFFu;
     if (i < PP.n) {
-      const KfwKey k = keys[i];
+      const Key k = keys[i];
       const int px = kfw_f2i(roundf((k.x - PP.minX) * PP.wInv));  // PosInGrid (:364-365)
       const int py = kfw_f2i(roundf((k.y - PP.minY) * PP.hInv));
       if (!(px < 0 || px >= KFW_COLS || py < 0 || py >= KFW_ROWS))
@@ -85,7 +91,7 @@ __global__ __launch_bounds__(1024) void k_kfwin_grid(const KfwProblem* __restric
     const uint32_t key = sk[i];
     if (key == 0xFFFFFFFFu) continue;
     const int idx = (int)(key & 0xFFFFu);
-    const KfwKey k = keys[idx];
+    const Key k = keys[idx];
     const uint4* dp = reinterpret_cast<const uint4*>(desc + (size_t)idx * 32);
     const uint4 d0 = dp[0], d1 = dp[1];
     uint4* out = reinterpret_cast<uint4*>(rec + i);
@@ -95,20 +101,25 @@ __global__ __launch_bounds__(1024) void k_kfwin_grid(const KfwProblem* __restric
   }
 }
 
-__global__ __launch_bounds__(KFW_BLOCK) void k_kfwin_search(
-    const KfwProblem* __restrict__ probs, const orbx_kf_query* __restrict__ qs,
-    const int32_t* __restrict__ qoff, const int32_t* __restrict__ blk_prob,
-    const uint8_t* __restrict__ qdesc, int nq, int32_t* __restrict__ best_idx,
-    int32_t* __restrict__ best_dist) {
-  const int gl = threadIdx.x & (KFW_G - 1);
-  const int qi = blockIdx.x * (KFW_BLOCK / KFW_G) + (threadIdx.x / KFW_G);
-  if (qi >= nq) return;  // whole groups leave: the shuffles below stay inside a group
-  // the problem of the block's first query comes from the host's table; the
-  // few problem boundaries inside a block are walked (qi < nq = qoff[nprob])
-  int p = blk_prob[blockIdx.x];
-  while (qi >= qoff[p + 1]) ++p;
-  const KfwProblem PP = probs[p];
-  const orbx_kf_query Q = qs[qi];
+__global__ __launch_bounds__(1024) void k_kfwin_grid(const KfwProblem* __restrict__ probs) {
+  __shared__ uint32_t sk[KFW_MAXN];  // cell << 16 | index, 0xFFFFFFFF = in no cell
+  const KfwProblem PP = probs[blockIdx.x];
+  kfwin_grid<KfwKey>(PP, sk);
+}
+
+// the plan's form: one workgroup per problem, keys as orbx_keypoint rows
+__global__ __launch_bounds__(1024) void k_kfwin_grid_kp(const KfwPlanProblem* __restrict__ probs) {
+  __shared__ uint32_t sk[KFW_MAXN];
+  const KfwProblem PP = probs[blockIdx.x].kf;
+  kfwin_grid<orbx_keypoint>(PP, sk);
+}
+
+// one query by its lane group: Q's window in PP's records; lane 0 of the group
+// writes best_idx[qi] / best_dist[qi]
+__device__ __forceinline__ void kfwin_search_one(const KfwProblem& PP, const orbx_kf_query& Q,
+                                                 const uint8_t* __restrict__ qdesc, int gl, int qi,
+                                                 int32_t* __restrict__ best_idx,
+                                                 int32_t* __restrict__ best_dist) {
   const uint4* qd = reinterpret_cast<const uint4*>(qdesc + (size_t)Q.desc * 32);
   const uint4 q0 = qd[0], q1 = qd[1];
   const int* __restrict__ cell_off = PP.cell_off;
@@ -149,6 +160,44 @@ __global__ __launch_bounds__(KFW_BLOCK) void k_kfwin_search(
       best_dist[qi] = (int32_t)(best >> 16);
     }
   }
+}
+
+__global__ __launch_bounds__(KFW_BLOCK) void k_kfwin_search(
+    const KfwProblem* __restrict__ probs, const orbx_kf_query* __restrict__ qs,
+    const int32_t* __restrict__ qoff, const int32_t* __restrict__ blk_prob,
+    const uint8_t* __restrict__ qdesc, int nq, int32_t* __restrict__ best_idx,
+    int32_t* __restrict__ best_dist) {
+  const int gl = threadIdx.x & (KFW_G - 1);
+  const int qi = blockIdx.x * (KFW_BLOCK / KFW_G) + (threadIdx.x / KFW_G);
+  if (qi >= nq) return;  // whole groups leave: the shuffles below stay inside a group
+  // the problem of the block's first query comes from the host's table; the
+  // few problem boundaries inside a block are walked (qi < nq = qoff[nprob])
+  int p = blk_prob[blockIdx.x];
+  while (qi >= qoff[p + 1]) ++p;
+  const KfwProblem PP = probs[p];
+  const orbx_kf_query Q = qs[qi];
+  kfwin_search_one(PP, Q, qdesc, gl, qi, best_idx, best_dist);
+}
+
+// the plan's form: problems on blockIdx.y, each with its own queries, pool
+// and results (no flattening, so no offset or block tables).  A desc outside
+// the problem's pool is answered like an empty window, without a read
+__global__ __launch_bounds__(KFW_BLOCK) void k_kfwin_search_plan(const KfwPlanProblem* __restrict__ probs) {
+  const KfwPlanProblem& PL = probs[blockIdx.y];
+  const int nq = PL.nq;
+  const int gl = threadIdx.x & (KFW_G - 1);
+  const int qi = blockIdx.x * (KFW_BLOCK / KFW_G) + (threadIdx.x / KFW_G);
+  if (qi >= nq) return;  // whole groups leave
+  const KfwProblem PP = PL.kf;
+  const orbx_kf_query Q = PL.qs[qi];
+  if ((uint32_t)Q.desc >= (uint32_t)nq) {  // uniform over the group
+    if (gl == 0) {
+      PL.best_idx[qi] = -1;
+      PL.best_dist[qi] = INT_MAX;
+    }
+    return;
+  }
+  kfwin_search_one(PP, Q, PL.qdesc, gl, qi, PL.best_idx, PL.best_dist);
 }
 
 }  // namespace orbx

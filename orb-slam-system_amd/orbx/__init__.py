@@ -7,6 +7,7 @@ reference interfaces for tests and the benchmark:
   search_by_bow  ORBmatcher::SearchByBoW(KF, KF) (/root/reference/src/ORBmatcher.cc:278-366)
   search_for_triangulation  ORBmatcher::SearchForTriangulation, batched (ORBmatcher.cc:368-467)
   keyframe_search  the search of ORBmatcher::Fuse / SearchBySim3, batched (ORBmatcher.cc:532-551)
+  keyframe_project / KeyframePlan  their projection on the device, and both on device tensors
   search_for_initialization  ORBmatcher::SearchForInitialization, batched (ORBmatcher.cc:197-276)
   compute_stereo_matches  Frame::ComputeStereoMatches (/root/reference/src/Frame.cc:446-620)
   descriptor_distance_batch  ORBmatcher::DescriptorDistance (ORBmatcher.cc:896-908)
@@ -70,6 +71,8 @@ EXPORTED = [
     "orbm_search_for_initialization", "orbm_search_for_initialization_stats",
     "orbv_score", "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_erase", "orbv_db_clear",
     "orbv_db_size", "orbv_db_query", "orbv_db_query_batch", "orbv_db_query_batch_device",
+    "orbm_keyframe_project", "orbm_kf_plan_create", "orbm_kf_plan_destroy", "orbm_kf_plan_search",
+    "orbm_kf_plan_project", "orbm_kf_plan_project_search",
 ]
 
 
@@ -173,6 +176,30 @@ KF_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("radius", "<f4"), ("leve
                            ("desc", "<i4")])
 assert KF_QUERY_DTYPE.itemsize == ctypes.sizeof(KfQuery) == 20
 
+KF_FORM_FUSE, KF_FORM_SIM3 = 1, 2  # ORBX_KF_FORM_*
+KF_POINT_FIELDS = ("pos", "min_dist_inv", "max_dist_inv", "max_dist", "skip")
+
+
+class KfCamera(ctypes.Structure):  # orbx_kf_camera
+    _fields_ = [("Rcw", ctypes.c_float * 9), ("tcw", ctypes.c_float * 3), ("ow", ctypes.c_float * 3),
+                ("sR21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("min_x", ctypes.c_float), ("max_x", ctypes.c_float),
+                ("min_y", ctypes.c_float), ("max_y", ctypes.c_float), ("nlevels", ctypes.c_int),
+                ("scale_factors", ctypes.c_float * PROJ_MAX_LEVELS), ("log_scale_factor", ctypes.c_float)]
+
+
+class KfPoints(ctypes.Structure):  # orbx_kf_points
+    _fields_ = [(n, ctypes.c_void_p) for n in KF_POINT_FIELDS]
+
+
+class KfProblem(ctypes.Structure):  # orbx_kf_problem
+    _fields_ = [("camera", KfCamera), ("points", KfPoints), ("npts", ctypes.c_int), ("qdesc", ctypes.c_void_p),
+                ("frame", KfFrame), ("q", ctypes.c_void_p), ("level", ctypes.c_void_p),
+                ("n_live", ctypes.c_void_p), ("n_nonfinite", ctypes.c_void_p),
+                ("best_idx", ctypes.c_void_p), ("best_dist", ctypes.c_void_p)]
+
+
 class InitPair(ctypes.Structure):  # orbx_init_pair
     _fields_ = [("f1", KfFrame), ("f2", KfFrame), ("prev_matched", ctypes.c_void_p),
                 ("match12", ctypes.c_void_p)]
@@ -270,6 +297,12 @@ _sig = {
     "orbm_project_points": (I, [I, I, P, P, P, P, I, P, P, P, P]),
     "orbm_proj_plan_project": (I, [P, I, I, P, P, P]),
     "orbm_proj_plan_track": (I, [P, I, I, P, P, F, I, I, P]),
+    "orbm_keyframe_project": (I, [I, I, P, P, P, P, F, I, P, P, P]),
+    "orbm_kf_plan_create": (I, [I, I, I, I, P]),
+    "orbm_kf_plan_destroy": (I, [P]),
+    "orbm_kf_plan_search": (I, [P, I, P, P]),
+    "orbm_kf_plan_project": (I, [P, I, I, P, F, P]),
+    "orbm_kf_plan_project_search": (I, [P, I, I, P, F, P]),
     "orbm_compute_distinctive_descriptors": (I, [P, P, I, I, P]),
     "orbx_undistort_keypoints": (I, [P, I, P, P, I, I, P]),
     "orbx_selftest_sincos": (I, [P, I, P, P]),
@@ -976,6 +1009,140 @@ def project_points(mode, problems, th=1.0, viewing_cos_limit=0.5, level_rule=LEV
                     None if vc is None else vc[off:off + n].copy(), int(niv[i])))
         off += n
     return out
+
+
+_KF_POINT_DTYPES = dict(pos=np.float32, min_dist_inv=np.float32, max_dist_inv=np.float32, max_dist=np.float32,
+                        skip=np.uint8)
+
+
+def kf_camera(cam):
+    """orbx_kf_camera from a dict: Rcw (3x3), tcw (3), fx, fy, cx, cy, min_x,
+    max_x, min_y, max_y, scale_factors (nlevels), log_scale_factor, and ow (3;
+    the Fuse form) or sR21 (3x3) and t21 (3) (the SearchBySim3 form); what a
+    form does not read may be left out."""
+    if isinstance(cam, KfCamera):
+        return cam
+    sf = np.asarray(cam["scale_factors"], np.float32).reshape(-1)
+    if not 1 <= len(sf) <= PROJ_MAX_LEVELS:
+        raise OrbxError(ERR_ARG, "kf_camera: 1 .. %d scale factors expected" % PROJ_MAX_LEVELS)
+    c = KfCamera()
+    for n, k in (("Rcw", 9), ("tcw", 3), ("ow", 3), ("sR21", 9), ("t21", 3)):
+        if cam.get(n) is not None:
+            getattr(c, n)[:] = np.asarray(cam[n], np.float32).reshape(k).tolist()
+    for n in ("fx", "fy", "cx", "cy", "min_x", "max_x", "min_y", "max_y", "log_scale_factor"):
+        setattr(c, n, float(np.float32(cam[n])))
+    c.nlevels = len(sf)
+    c.scale_factors[:len(sf)] = sf.tolist()
+    return c
+
+
+def keyframe_project(form, problems, th=3.0, desc_base=None, device=0):
+    """orbm_keyframe_project on host arrays: the query rows of ORBmatcher::Fuse
+    (KF_FORM_FUSE) or SearchBySim3 (KF_FORM_SIM3) from map points and a pose.
+    problems: list of (camera dict, points dict of numpy arrays named as
+    KF_POINT_FIELDS); desc_base: None or one int per problem.  Returns per
+    problem (q KF_QUERY_DTYPE[npts], level int32[npts], n_live)."""
+    nprob = len(problems)
+    cams = (KfCamera * max(nprob, 1))()
+    pts = (KfPoints * max(nprob, 1))()
+    npts = np.zeros(max(nprob, 1), np.int32)
+    keep = []
+    for i, (cam, P) in enumerate(problems):
+        cams[i] = kf_camera(cam)
+        arrs = {n: np.ascontiguousarray(P[n], _KF_POINT_DTYPES[n]) for n in KF_POINT_FIELDS if P.get(n) is not None}
+        keep.append(arrs)
+        pts[i] = KfPoints(*[_p(arrs.get(n)) for n in KF_POINT_FIELDS])
+        npts[i] = len(np.asarray(P["pos"]).reshape(-1, 3))
+    base = None if desc_base is None else np.ascontiguousarray(desc_base, np.int32).reshape(-1)
+    if base is not None and len(base) != nprob:
+        raise OrbxError(ERR_ARG, "one desc_base per problem expected")
+    total = int(npts[:nprob].sum())
+    q = np.zeros(max(total, 1), KF_QUERY_DTYPE)
+    level = np.zeros(max(total, 1), np.int32)
+    nlive = np.zeros(max(nprob, 1), np.int32)
+    _check(_lib.orbm_keyframe_project(int(form), nprob, ctypes.cast(cams, ctypes.c_void_p),
+                                      ctypes.cast(pts, ctypes.c_void_p), _p(npts), _p(base), float(th), device,
+                                      _p(q), _p(level), _p(nlive)), "orbm_keyframe_project")
+    out, off = [], 0
+    for i in range(nprob):
+        n = int(npts[i])
+        out.append((q[off:off + n].copy(), level[off:off + n].copy(), int(nlive[i])))
+        off += n
+    return out
+
+
+class KeyframePlan:
+    """orbm_kf_plan: the projection of ORBmatcher::Fuse / SearchBySim3 and the
+    keyframe window search on device-resident data, asynchronous.  A problem
+    is a dict of cuda tensors and host values:
+      camera   a kf_camera dict (host values)             [project]
+      points   dict: pos [npts, 3] f32, min_dist_inv, max_dist_inv, max_dist
+               [npts] f32, skip [npts] u8 or absent        [project]
+      npts     the point / query count (taken from points["pos"] or q if absent)
+      qdesc    [npts, 32] u8                               [search]
+      frame    dict: keys [n, 28] u8 (orbx_keypoint rows), desc [n, 32] u8, and
+               the floats min_x, min_y, grid_w_inv, grid_h_inv   [search]
+      q        [npts, 20] u8 (KF_QUERY_DTYPE rows): input of search(), output
+               of project(), optional output of project_search()
+      level    [npts] i32: output of project(), optional for project_search()
+      n_live, n_nonfinite   [1] i32, optional outputs      [project]
+      best_idx, best_dist   [npts] i32 outputs             [search]
+    Point arrays and qdesc of different problems may be the same tensors."""
+
+    def __init__(self, max_problems, max_n, max_queries, device=0):
+        h = ctypes.c_void_p()
+        _check(_lib.orbm_kf_plan_create(max_problems, max_n, max_queries, device, ctypes.byref(h)),
+               "orbm_kf_plan_create")
+        self._h, self.device = h, device
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.orbm_kf_plan_destroy(self._h)
+            self._h = None
+
+    @staticmethod
+    def _problems(problems, project, search):
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+        arr = (KfProblem * max(len(problems), 1))()
+        for i, pb in enumerate(problems):
+            a = arr[i]
+            pts = pb.get("points") or {}
+            if "npts" in pb:
+                a.npts = int(pb["npts"])
+            elif project:
+                a.npts = pts["pos"].shape[0]
+            else:
+                a.npts = pb["q"].shape[0]
+            if project:
+                a.camera = kf_camera(pb["camera"])
+                a.points = KfPoints(*[ptr(pts.get(n)) for n in KF_POINT_FIELDS])
+            if search:
+                fr = pb["frame"]
+                a.frame = KfFrame(fr["keys"].shape[0], ptr(fr["keys"]), ptr(fr["desc"]), fr["min_x"], fr["min_y"],
+                                  fr["grid_w_inv"], fr["grid_h_inv"])
+            for n in ("qdesc", "q", "level", "n_live", "n_nonfinite", "best_idx", "best_dist"):
+                setattr(a, n, ptr(pb.get(n)))
+        return arr
+
+    def search(self, problems, stream=None):
+        """orbm_kf_plan_search: orbm_keyframe_search's search over the rows in q."""
+        arr = self._problems(problems, False, True)
+        _check(_lib.orbm_kf_plan_search(self._h, len(problems), ctypes.cast(arr, ctypes.c_void_p),
+                                        _stream_handle(stream)), "orbm_kf_plan_search")
+
+    def project(self, form, problems, th=3.0, stream=None):
+        """orbm_kf_plan_project: the query rows only."""
+        arr = self._problems(problems, True, False)
+        _check(_lib.orbm_kf_plan_project(self._h, int(form), len(problems), ctypes.cast(arr, ctypes.c_void_p),
+                                         float(th), _stream_handle(stream)), "orbm_kf_plan_project")
+
+    def project_search(self, form, problems, th=3.0, stream=None):
+        """orbm_kf_plan_project_search: project() then search() on one stream."""
+        arr = self._problems(problems, True, True)
+        _check(_lib.orbm_kf_plan_project_search(self._h, int(form), len(problems),
+                                                ctypes.cast(arr, ctypes.c_void_p), float(th),
+                                                _stream_handle(stream)), "orbm_kf_plan_project_search")
 
 
 def compute_distinctive_descriptors(groups, device=0):
