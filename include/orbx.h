@@ -930,6 +930,64 @@ int orbm_kf_plan_project_search(orbm_kf_plan* plan, int form, int nprob,
                                 const orbx_kf_problem* problems, float th, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Optimizer::PoseOptimization (src/Optimizer.cc:220-432), batched (DESIGN.md
+ * §19): the four rounds of g2o's Levenberg loop over one 6-DoF vertex and the
+ * frame's unary reprojection edges, one launch for all problems.  Sums over
+ * edges are taken in the fixed device order of DESIGN §19, not in edge order.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  float Tcw[12];               /* rows 0..2 of mTcw */
+  float fx, fy, cx, cy, mbf;
+  int nlevels;                 /* 1 .. ORBX_PROJ_MAX_LEVELS */
+  float inv_level_sigma2[ORBX_PROJ_MAX_LEVELS];   /* mvInvLevelSigma2 */
+} orbx_pose_camera;
+
+typedef struct {
+  int n;                       /* Frame::N, <= 8192 */
+  const orbx_keypoint* keys;   /* mvKeysUn: pt and octave are read */
+  const float* uright;         /* mvuRight; NULL = all monocular */
+  const float* pos;            /* world positions, [n][3] or a pool */
+  const int32_t* point_index;  /* NULL: feature i uses pos[i] where has_point[i];
+                                  else pos[point_index[i]], -1 = no point.  This is
+                                  orbm_proj_plan_track's match[] as it stands */
+  const uint8_t* has_point;    /* read only when point_index is NULL; NULL = all */
+  int npos;                    /* pool size, bounds point_index */
+} orbx_pose_obs;
+
+#define ORBX_POSE_MAX_N 8192
+/* Host pointers; synchronous.  Tcw_out[p] = the 4x4 pose (row-major),
+ * outlier = mvbOutlier of every problem, concatenated (sum of n; 0 where a
+ * feature has no point), ninliers[p] = the return value.  Where the reference
+ * returns 0 (fewer than 3 correspondences) ninliers[p] = 0 and Tcw_out[p] is
+ * the input pose.  nprob == 0 and n == 0 are valid.  ORBX_ERR_ARG, with no
+ * output written, for a bad count (nprob, n, npos, nlevels), an octave outside
+ * [0, nlevels), a point_index outside [-1, npos), npos < n without
+ * point_index, or a required pointer that is NULL. */
+int orbm_pose_optimization(int nprob, const orbx_pose_camera* cameras, const orbx_pose_obs* obs,
+                           int device, float* Tcw_out, uint8_t* outlier, int* ninliers);
+
+/* The same on device memory, asynchronous on `stream`: every pointer of obs and
+ * the four outputs are device pointers; the problem table itself is host
+ * memory, staged by the call.  Tcw_out[16], outlier[obs.n], ninliers (one int)
+ * and status (one int) are written per problem.  A feature with a bad octave or
+ * point index cannot be refused here: it is taken as having no point and
+ * counted in *status (0 = none).  One host thread per plan; calls on different
+ * streams are ordered by the plan as orbm_proj_plan_search's are.  It may
+ * follow orbm_proj_plan_track on the same stream with point_index = match. */
+typedef struct {
+  orbx_pose_camera camera;
+  orbx_pose_obs obs;
+  float* Tcw_out;
+  uint8_t* outlier;
+  int* ninliers;
+  int* status;
+} orbx_pose_problem;
+typedef struct orbm_pose_plan orbm_pose_plan;
+int orbm_pose_plan_create(int max_problems, int max_n, int device, orbm_pose_plan** out);
+int orbm_pose_plan_destroy(orbm_pose_plan* plan);
+int orbm_pose_plan_optimize(orbm_pose_plan* plan, int nprob, const orbx_pose_problem* problems, void* stream);
+
+/* ---------------------------------------------------------------------------
  * SURVEY.md §8f rank 4.
  * ------------------------------------------------------------------------- */
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:222-271), batched

@@ -1665,6 +1665,89 @@ void ComputeStereoMatches(FR& F) {
              "ComputeStereoMatches");
 }
 
+// Optimizer::PoseOptimization (src/Optimizer.cc:220-432) on the device
+// (orbm_pose_optimization).  FR: the reference's Frame -- reads
+// mTcw, N, mvpMapPoints (GetWorldPos()), mvKeysUn, mvuRight, mvInvLevelSigma2,
+// fx fy cx cy mbf; writes mvbOutlier of the features with a map point, calls
+// SetPose and returns the inlier count.  With fewer than 3 correspondences it
+// returns 0 with those flags cleared and the pose as it was.  The batched
+// overload runs every frame in one launch.
+class Optimizer {
+ public:
+  template <class FR>
+  static int PoseOptimization(FR* pFrame, int device = 0) {
+    std::vector<FR*> one(1, pFrame);
+    return PoseOptimization(one, device)[0];
+  }
+
+  template <class FR>
+  static std::vector<int> PoseOptimization(const std::vector<FR*>& vpFrames, int device = 0) {
+    const size_t nf = vpFrames.size();
+    std::vector<orbx_pose_camera> cams(nf);
+    std::vector<orbx_pose_obs> obs(nf);
+    std::vector<std::vector<float> > pos(nf);
+    std::vector<std::vector<uint8_t> > has(nf);
+    size_t total = 0;
+    for (size_t f = 0; f < nf; ++f) {
+      FR& F = *vpFrames[f];
+      orbx_pose_camera& C = cams[f];
+      memset(&C, 0, sizeof(C));
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) C.Tcw[4 * r + c] = F.mTcw.template at<float>(r, c);
+      C.fx = F.fx;
+      C.fy = F.fy;
+      C.cx = F.cx;
+      C.cy = F.cy;
+      C.mbf = F.mbf;
+      C.nlevels = (int)F.mvInvLevelSigma2.size();
+      if (C.nlevels < 1 || C.nlevels > ORBX_PROJ_MAX_LEVELS) orbx_throw(ORBX_ERR_ARG, "PoseOptimization");
+      for (int l = 0; l < C.nlevels; ++l) C.inv_level_sigma2[l] = F.mvInvLevelSigma2[l];
+      const int N = F.N;
+      pos[f].assign((size_t)N * 3, 0.0f);
+      has[f].assign((size_t)N, 0);
+      for (int i = 0; i < N; ++i) {
+        auto* pMP = F.mvpMapPoints[i];
+        if (!pMP) continue;
+        const cv::Mat Xw = pMP->GetWorldPos();
+        for (int c = 0; c < 3; ++c) pos[f][3 * (size_t)i + c] = Xw.template at<float>(c);
+        has[f][i] = 1;
+      }
+      orbx_pose_obs& O = obs[f];
+      memset(&O, 0, sizeof(O));
+      O.n = N;
+      O.keys = reinterpret_cast<const orbx_keypoint*>(F.mvKeysUn.data());
+      O.uright = F.mvuRight.data();
+      O.pos = pos[f].data();
+      O.has_point = has[f].data();
+      O.npos = N;
+      total += (size_t)N;
+    }
+    std::vector<float> T(nf * 16);
+    std::vector<uint8_t> outlier(total ? total : 1);
+    std::vector<int> ninliers(nf);
+    orbx_throw(orbm_pose_optimization((int)nf, cams.data(), obs.data(), device, T.data(), outlier.data(),
+                                      ninliers.data()),
+               "PoseOptimization");
+    size_t off = 0;
+    for (size_t f = 0; f < nf; ++f) {
+      FR& F = *vpFrames[f];
+      int ncorr = 0;
+      for (int i = 0; i < F.N; ++i)
+        if (has[f][i]) {
+          F.mvbOutlier[i] = outlier[off + i] != 0;
+          ++ncorr;
+        }
+      off += (size_t)F.N;
+      if (ncorr < 3) continue;  // Optimizer.cc:345-346: the pose is not written
+      cv::Mat pose(4, 4, CV_32F);
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) pose.at<float>(r, c) = T[16 * f + 4 * r + c];
+      F.SetPose(pose);
+    }
+    return ninliers;
+  }
+};
+
 }  // namespace ORB_SLAM2
 
 #endif

@@ -73,6 +73,7 @@ EXPORTED = [
     "orbv_db_size", "orbv_db_query", "orbv_db_query_batch", "orbv_db_query_batch_device",
     "orbm_keyframe_project", "orbm_kf_plan_create", "orbm_kf_plan_destroy", "orbm_kf_plan_search",
     "orbm_kf_plan_project", "orbm_kf_plan_project_search",
+    "orbm_pose_optimization", "orbm_pose_plan_create", "orbm_pose_plan_destroy", "orbm_pose_plan_optimize",
 ]
 
 
@@ -146,6 +147,26 @@ class ProjBuildProblem(ctypes.Structure):  # orbx_proj_build_problem
                 ("q", ctypes.c_void_p), ("level", ctypes.c_void_p), ("view_cos", ctypes.c_void_p),
                 ("n_in_view", ctypes.c_void_p), ("n_nonfinite", ctypes.c_void_p), ("frame", ProjFrame),
                 ("qdesc", ctypes.c_void_p), ("match", ctypes.c_void_p), ("nmatches", ctypes.c_void_p)]
+
+
+class PoseCamera(ctypes.Structure):  # orbx_pose_camera
+    _fields_ = [("Tcw", ctypes.c_float * 12), ("fx", ctypes.c_float), ("fy", ctypes.c_float),
+                ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("mbf", ctypes.c_float), ("nlevels", ctypes.c_int),
+                ("inv_level_sigma2", ctypes.c_float * PROJ_MAX_LEVELS)]
+
+
+class PoseObs(ctypes.Structure):  # orbx_pose_obs
+    _fields_ = [("n", ctypes.c_int), ("keys", ctypes.c_void_p), ("uright", ctypes.c_void_p),
+                ("pos", ctypes.c_void_p), ("point_index", ctypes.c_void_p), ("has_point", ctypes.c_void_p),
+                ("npos", ctypes.c_int)]
+
+
+class PoseProblem(ctypes.Structure):  # orbx_pose_problem
+    _fields_ = [("camera", PoseCamera), ("obs", PoseObs), ("Tcw_out", ctypes.c_void_p),
+                ("outlier", ctypes.c_void_p), ("ninliers", ctypes.c_void_p), ("status", ctypes.c_void_p)]
+
+
+POSE_MAX_N = 8192  # ORBX_POSE_MAX_N
 
 
 class BowFrame(ctypes.Structure):
@@ -303,6 +324,10 @@ _sig = {
     "orbm_kf_plan_search": (I, [P, I, P, P]),
     "orbm_kf_plan_project": (I, [P, I, I, P, F, P]),
     "orbm_kf_plan_project_search": (I, [P, I, I, P, F, P]),
+    "orbm_pose_optimization": (I, [I, P, P, I, P, P, P]),
+    "orbm_pose_plan_create": (I, [I, I, I, P]),
+    "orbm_pose_plan_destroy": (I, [P]),
+    "orbm_pose_plan_optimize": (I, [P, I, P, P]),
     "orbm_compute_distinctive_descriptors": (I, [P, P, I, I, P]),
     "orbx_undistort_keypoints": (I, [P, I, P, P, I, I, P]),
     "orbx_selftest_sincos": (I, [P, I, P, P]),
@@ -1143,6 +1168,104 @@ class KeyframePlan:
         _check(_lib.orbm_kf_plan_project_search(self._h, int(form), len(problems),
                                                 ctypes.cast(arr, ctypes.c_void_p), float(th),
                                                 _stream_handle(stream)), "orbm_kf_plan_project_search")
+
+
+def pose_camera(cam):
+    """orbx_pose_camera from a dict: Tcw (3x4 or 4x4, rows 0..2 used), fx, fy,
+    cx, cy, mbf, inv_level_sigma2 (nlevels)."""
+    if isinstance(cam, PoseCamera):
+        return cam
+    sg = np.asarray(cam["inv_level_sigma2"], np.float32).reshape(-1)
+    if not 1 <= len(sg) <= PROJ_MAX_LEVELS:
+        raise OrbxError(ERR_ARG, "pose_camera: 1 .. %d levels expected" % PROJ_MAX_LEVELS)
+    c = PoseCamera()
+    c.Tcw[:] = np.asarray(cam["Tcw"], np.float32).reshape(-1, 4)[:3].reshape(12).tolist()
+    for n in ("fx", "fy", "cx", "cy", "mbf"):
+        setattr(c, n, float(np.float32(cam[n])))
+    c.nlevels = len(sg)
+    c.inv_level_sigma2[:len(sg)] = sg.tolist()
+    return c
+
+
+def pose_optimization(problems, device=0):
+    """orbm_pose_optimization (Optimizer::PoseOptimization, batched) on host
+    arrays.  problems: list of (camera dict as pose_camera takes, obs dict):
+    keys KEYPOINT_DTYPE[n], pos float32[npos, 3], and optionally uright
+    float32[n], point_index int32[n] (-1 = no point) or has_point uint8[n].
+    Returns per problem (Tcw float32[4, 4], outlier uint8[n], ninliers)."""
+    nprob = len(problems)
+    cams = (PoseCamera * max(nprob, 1))()
+    obs = (PoseObs * max(nprob, 1))()
+    keep, ns = [], []
+    for i, (cam, O) in enumerate(problems):
+        cams[i] = pose_camera(cam)
+        keys = np.ascontiguousarray(O["keys"], KEYPOINT_DTYPE).reshape(-1)
+        pos = np.ascontiguousarray(O["pos"], np.float32).reshape(-1, 3)
+        opt = {k: np.ascontiguousarray(O[k], t).reshape(-1)
+               for k, t in (("uright", np.float32), ("point_index", np.int32), ("has_point", np.uint8))
+               if O.get(k) is not None}
+        for k, a in opt.items():
+            if len(a) != len(keys):
+                raise OrbxError(ERR_ARG, "pose_optimization: %s has %d entries for %d keys" % (k, len(a), len(keys)))
+        keep.append((keys, pos, opt))
+        obs[i] = PoseObs(len(keys), _p(keys), _p(opt.get("uright")), _p(pos), _p(opt.get("point_index")),
+                         _p(opt.get("has_point")), len(pos))
+        ns.append(len(keys))
+    total = sum(ns)
+    T = np.zeros((max(nprob, 1), 4, 4), np.float32)
+    outlier = np.zeros(max(total, 1), np.uint8)
+    nin = np.zeros(max(nprob, 1), np.int32)
+    _check(_lib.orbm_pose_optimization(nprob, ctypes.cast(cams, ctypes.c_void_p), ctypes.cast(obs, ctypes.c_void_p),
+                                       device, _p(T), _p(outlier), _p(nin)), "orbm_pose_optimization")
+    out, off = [], 0
+    for i, n in enumerate(ns):
+        out.append((T[i].copy(), outlier[off:off + n].copy(), int(nin[i])))
+        off += n
+    return out
+
+
+class PosePlan:
+    """Batched Optimizer::PoseOptimization on device-resident data
+    (orbm_pose_plan_*): one launch for all problems, asynchronous."""
+
+    def __init__(self, max_problems, max_n, device=0):
+        h = ctypes.c_void_p()
+        _check(_lib.orbm_pose_plan_create(max_problems, max_n, device, ctypes.byref(h)), "orbm_pose_plan_create")
+        self._h, self.device = h, device
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _lib.orbm_pose_plan_destroy(self._h)
+            self._h = None
+
+    def optimize(self, problems, stream=None):
+        """problems: list of dicts -- camera (a pose_camera dict: host values)
+        and cuda tensors keys [n, 28] u8 (orbx_keypoint rows), pos [npos, 3]
+        f32, optionally uright [n] f32, point_index [n] i32 (-1 = no point; the
+        match[] of ProjPlan.track as it stands) or has_point [n] u8, and the
+        outputs Tcw_out [16] f32, outlier [n] u8, ninliers [1] i32 and status
+        [1] i32 (features dropped for a bad octave or index)."""
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+        arr = (PoseProblem * max(len(problems), 1))()
+        for i, pb in enumerate(problems):
+            n = pb["keys"].shape[0]
+            _check_dev(pb["keys"], 1, n, "keys", (28,))
+            _check_dev(pb["pos"], 4, 0, "pos", (3,))
+            for k, sz in (("uright", 4), ("point_index", 4), ("has_point", 1), ("outlier", 1)):
+                if pb.get(k) is not None:
+                    _check_dev(pb[k], sz, n, k)
+            _check_dev(pb["Tcw_out"], 4, 16, "Tcw_out")
+            _check_dev(pb["ninliers"], 4, 1, "ninliers")
+            _check_dev(pb["status"], 4, 1, "status")
+            a = arr[i]
+            a.camera = pose_camera(pb["camera"])
+            a.obs = PoseObs(n, ptr(pb["keys"]), ptr(pb.get("uright")), ptr(pb["pos"]), ptr(pb.get("point_index")),
+                            ptr(pb.get("has_point")), pb["pos"].shape[0])
+            a.Tcw_out, a.outlier = ptr(pb["Tcw_out"]), ptr(pb.get("outlier"))
+            a.ninliers, a.status = ptr(pb["ninliers"]), ptr(pb["status"])
+        _check(_lib.orbm_pose_plan_optimize(self._h, len(problems), ctypes.cast(arr, ctypes.c_void_p),
+                                            _stream_handle(stream)), "orbm_pose_plan_optimize")
 
 
 def compute_distinctive_descriptors(groups, device=0):
