@@ -988,6 +988,45 @@ int orbm_pose_plan_destroy(orbm_pose_plan* plan);
 int orbm_pose_plan_optimize(orbm_pose_plan* plan, int nprob, const orbx_pose_problem* problems, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Initializer::FindHomography / FindFundamental (src/Initializer.cc:80-404),
+ * batched over frame pairs: nit RANSAC hypotheses of each
+ * model per pair (8-point DLT, symmetric transfer / epipolar score of every
+ * match), the winners, their inlier flags and RH = SH / (SH + SF), which is
+ * Initialize (:16-72) up to the choice of the model.  ReconstructH / ReconstructF
+ * stay with the caller.  The SVD, the 3x3 products and the inverses are this
+ * library's own fixed forms ("unpinned"), not OpenCV's.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int n1, n2;
+  const orbx_keypoint* keys1;  /* mvKeysUn of the reference frame (pt read) */
+  const orbx_keypoint* keys2;  /* mvKeysUn of the current frame */
+  const int32_t* match12;      /* n1, as orbm_search_for_initialization leaves it */
+  const int32_t* sets;         /* nit * 8, indices into the match list (mvSets) */
+} orbx_ransac_pair;
+
+typedef struct {
+  float H21[9], F21[9];        /* row-major; zeros where the winner is absent */
+  float SH, SF, RH;
+  int32_t it_H, it_F;          /* winning iteration, -1 for none */
+  int32_t nmatch;
+} orbx_ransac_result;
+
+/* Host pointers; synchronous; safe from several threads.  The match list
+ * (mvMatches12) of a pair holds the rows with match12[i] >= 0 in ascending i;
+ * inliers_H / inliers_F receive one flag per entry of it, nmatch of them, at
+ * inl_off[p] (inl_off has npair + 1 entries; bytes past nmatch are not
+ * written).  A model none of whose hypotheses scores above 0 has it = -1, a
+ * zero matrix, score 0 and all flags 0; RH is NaN for 0 / 0.  npair == 0 and
+ * nit == 0 are valid.  ORBX_ERR_ARG, with no output written, for npair < 0,
+ * nit < 0, a required pointer that is NULL, a non-finite key coordinate or
+ * sigma, a match12 entry >= n2, a set index outside [0, nmatch), fewer than 8
+ * matches in a pair, or inl_off[p + 1] - inl_off[p] < nmatch;
+ * ORBX_ERR_UNSUPPORTED for n1 or n2 > 8192, nit > 4096 or npair > 65535. */
+int orbm_initializer_ransac(int npair, const orbx_ransac_pair* pairs, int nit, float sigma, int device,
+                            orbx_ransac_result* res,
+                            uint8_t* inliers_H, uint8_t* inliers_F, const int32_t* inl_off /* npair + 1 */);
+
+/* ---------------------------------------------------------------------------
  * SURVEY.md §8f rank 4.
  * ------------------------------------------------------------------------- */
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:222-271), batched

@@ -1748,6 +1748,183 @@ class Optimizer {
   }
 };
 
+// Initializer (include/Initializer.h, src/Initializer.cc) up to the choice of
+// the model, on the device (orbm_initializer_ransac): the
+// reference's constructor, the match list and index draw of Initialize
+// (:19-63, SetMatches here), and FindHomography / FindFundamental with the
+// reference's signatures.  Initialize itself is not provided: ReconstructH /
+// ReconstructF (:406-865) stay with the caller, who takes RH() and the winning
+// model's matrix and flags there (INTEGRATION.md has the call site).  One
+// device call computes both models; the two Find* members share its result, so
+// the reference's two threads (:68-71) may call them concurrently.  FR: the
+// reference's Frame -- reads mK and mvKeysUn.
+class Initializer {
+ public:
+  typedef std::pair<int, int> Match;
+
+  template <class FR>
+  Initializer(const FR& ReferenceFrame, float sigma = 1.0, int iterations = 200) {
+    mK = ReferenceFrame.mK.clone();
+    mvKeys1 = ReferenceFrame.mvKeysUn;
+    mSigma = sigma;
+    mSigma2 = sigma * sigma;
+    mMaxIterations = iterations;
+  }
+
+  // DUtils::Random::SeedRandOnce(int) and RandomInt
+  // (Thirdparty/DBoW2/DUtils/Random.cpp:38-50): one srand per process
+  static void SeedRandOnce(int seed) {
+    static bool already_seeded = false;
+    if (!already_seeded) {
+      srand((unsigned)seed);
+      already_seeded = true;
+    }
+  }
+  static int RandomInt(int min, int max) {
+    const int d = max - min + 1;
+    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+  }
+
+  // Initialize :19-63: mvKeys2, mvMatches12, mvbMatched1 and the mvSets draw
+  // with rand().  Fewer than 8 matches: the reference's draw runs its index
+  // vector empty; here it throws instead
+  template <class FR>
+  void SetMatches(const FR& CurrentFrame, const std::vector<int>& vMatches12) {
+    std::lock_guard<std::mutex> lk(mMutex);
+    mbComputed = false;
+    mvKeys2 = CurrentFrame.mvKeysUn;
+    mvIniMatches.assign(vMatches12.begin(), vMatches12.end());
+    mvMatches12.clear();
+    mvMatches12.reserve(mvKeys2.size());
+    mvbMatched1.resize(mvKeys1.size());
+    for (size_t i = 0, iend = vMatches12.size(); i < iend; i++) {
+      if (vMatches12[i] >= 0) {
+        mvMatches12.push_back(std::make_pair((int)i, vMatches12[i]));
+        mvbMatched1[i] = true;
+      } else {
+        mvbMatched1[i] = false;
+      }
+    }
+    const int N = (int)mvMatches12.size();
+    if (N < 8) orbx_throw(ORBX_ERR_ARG, "Initializer: fewer than 8 matches");
+    std::vector<size_t> vAllIndices;
+    vAllIndices.reserve(N);
+    std::vector<size_t> vAvailableIndices;
+    for (int i = 0; i < N; i++) vAllIndices.push_back(i);
+    mvSets = std::vector<std::vector<size_t> >(mMaxIterations, std::vector<size_t>(8, 0));
+    SeedRandOnce(0);
+    for (int it = 0; it < mMaxIterations; it++) {
+      vAvailableIndices = vAllIndices;
+      for (size_t j = 0; j < 8; j++) {
+        const int randi = RandomInt(0, (int)vAvailableIndices.size() - 1);
+        const int idx = (int)vAvailableIndices[randi];
+        mvSets[it][j] = idx;
+        vAvailableIndices[randi] = vAvailableIndices.back();
+        vAvailableIndices.pop_back();
+      }
+    }
+  }
+
+  // :80-122 and :126-167.  With no hypothesis scoring above 0 the matrix is
+  // left as it was, as the reference leaves it
+  void FindHomography(std::vector<bool>& vbMatchesInliers, float& score, cv::Mat& H21, int device = 0) {
+    Compute(device);
+    Report(mResult.H21, mResult.SH, mResult.it_H, mvInliersH, vbMatchesInliers, score, H21);
+  }
+  void FindFundamental(std::vector<bool>& vbMatchesInliers, float& score, cv::Mat& F21, int device = 0) {
+    Compute(device);
+    Report(mResult.F21, mResult.SF, mResult.it_F, mvInliersF, vbMatchesInliers, score, F21);
+  }
+  // SH / (SH + SF) of :72 and the whole result record
+  float RH(int device = 0) {
+    Compute(device);
+    return mResult.RH;
+  }
+  const orbx_ransac_result& Result(int device = 0) {
+    Compute(device);
+    return mResult;
+  }
+
+  // Both models of several initializers (each after its SetMatches) in one
+  // device call; their Find* members then only report.  All must share sigma
+  // and the iteration count
+  static void FindModels(const std::vector<Initializer*>& vpInit, int device = 0) {
+    const size_t n = vpInit.size();
+    if (n == 0) return;
+    std::vector<std::unique_lock<std::mutex> > locks;
+    for (Initializer* I : vpInit) locks.emplace_back(I->mMutex);
+    std::vector<orbx_ransac_pair> pairs(n);
+    std::vector<std::vector<int32_t> > sets(n);
+    std::vector<int32_t> off(n + 1, 0);
+    const int nit = vpInit[0]->mMaxIterations;
+    const float sigma = vpInit[0]->mSigma;
+    for (size_t p = 0; p < n; ++p) {
+      Initializer& I = *vpInit[p];
+      if (I.mMaxIterations != nit || I.mSigma != sigma || (int)I.mvSets.size() != nit ||
+          I.mvIniMatches.size() != I.mvKeys1.size())
+        orbx_throw(ORBX_ERR_ARG, "Initializer::FindModels");
+      sets[p].reserve((size_t)nit * 8);
+      for (const std::vector<size_t>& s : I.mvSets)
+        for (size_t v : s) sets[p].push_back((int32_t)v);
+      pairs[p].n1 = (int)I.mvKeys1.size();
+      pairs[p].n2 = (int)I.mvKeys2.size();
+      pairs[p].keys1 = reinterpret_cast<const orbx_keypoint*>(I.mvKeys1.data());
+      pairs[p].keys2 = reinterpret_cast<const orbx_keypoint*>(I.mvKeys2.data());
+      pairs[p].match12 = I.mvIniMatches.data();
+      pairs[p].sets = sets[p].data();
+      off[p + 1] = off[p] + (int32_t)I.mvMatches12.size();
+    }
+    std::vector<orbx_ransac_result> res(n);
+    std::vector<uint8_t> inlH((size_t)off[n] + 1), inlF((size_t)off[n] + 1);
+    orbx_throw(orbm_initializer_ransac((int)n, pairs.data(), nit, sigma, device, res.data(), inlH.data(),
+                                       inlF.data(), off.data()),
+               "Initializer::FindModels");
+    for (size_t p = 0; p < n; ++p) {
+      Initializer& I = *vpInit[p];
+      I.mResult = res[p];
+      I.mvInliersH.assign(inlH.begin() + off[p], inlH.begin() + off[p + 1]);
+      I.mvInliersF.assign(inlF.begin() + off[p], inlF.begin() + off[p + 1]);
+      I.mbComputed = true;
+    }
+  }
+
+  // the reference's members (include/Initializer.h:60-80)
+  std::vector<cv::KeyPoint> mvKeys1, mvKeys2;
+  std::vector<Match> mvMatches12;
+  std::vector<bool> mvbMatched1;
+  cv::Mat mK;
+  float mSigma, mSigma2;
+  int mMaxIterations;
+  std::vector<std::vector<size_t> > mvSets;
+
+ private:
+  void Compute(int device) {
+    std::lock_guard<std::mutex> once(mComputeMutex);  // the second of two threads waits, then reports
+    {
+      std::lock_guard<std::mutex> lk(mMutex);
+      if (mbComputed) return;
+    }
+    FindModels(std::vector<Initializer*>(1, this), device);
+  }
+  void Report(const float M[9], float S, int it, const std::vector<uint8_t>& inl, std::vector<bool>& vbMatchesInliers,
+              float& score, cv::Mat& M21) {
+    std::lock_guard<std::mutex> lk(mMutex);
+    vbMatchesInliers.assign(inl.size(), false);
+    for (size_t i = 0; i < inl.size(); ++i) vbMatchesInliers[i] = inl[i] != 0;
+    score = S;
+    if (it < 0) return;
+    M21.create(3, 3, CV_32F);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) M21.at<float>(r, c) = M[3 * r + c];
+  }
+
+  std::vector<int32_t> mvIniMatches;  // vMatches12 as given: the ABI's match12
+  std::mutex mMutex, mComputeMutex;
+  bool mbComputed = false;
+  orbx_ransac_result mResult;
+  std::vector<uint8_t> mvInliersH, mvInliersF;
+};
+
 }  // namespace ORB_SLAM2
 
 #endif

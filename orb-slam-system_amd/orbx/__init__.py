@@ -74,6 +74,7 @@ EXPORTED = [
     "orbm_keyframe_project", "orbm_kf_plan_create", "orbm_kf_plan_destroy", "orbm_kf_plan_search",
     "orbm_kf_plan_project", "orbm_kf_plan_project_search",
     "orbm_pose_optimization", "orbm_pose_plan_create", "orbm_pose_plan_destroy", "orbm_pose_plan_optimize",
+    "orbm_initializer_ransac",
 ]
 
 
@@ -226,6 +227,16 @@ class InitPair(ctypes.Structure):  # orbx_init_pair
                 ("match12", ctypes.c_void_p)]
 
 
+class RansacPair(ctypes.Structure):  # orbx_ransac_pair
+    _fields_ = [("n1", ctypes.c_int), ("n2", ctypes.c_int), ("keys1", ctypes.c_void_p), ("keys2", ctypes.c_void_p),
+                ("match12", ctypes.c_void_p), ("sets", ctypes.c_void_p)]
+
+
+# orbx_ransac_result
+RANSAC_RESULT_DTYPE = np.dtype([("H21", "<f4", (3, 3)), ("F21", "<f4", (3, 3)), ("SH", "<f4"), ("SF", "<f4"),
+                                ("RH", "<f4"), ("it_H", "<i4"), ("it_F", "<i4"), ("nmatch", "<i4")])
+
+
 # k_init_cand's list length per row and the feature limit (csrc/init_internal.h)
 INIT_T, INIT_MAXN = 8, 8192
 
@@ -328,6 +339,7 @@ _sig = {
     "orbm_pose_plan_create": (I, [I, I, I, P]),
     "orbm_pose_plan_destroy": (I, [P]),
     "orbm_pose_plan_optimize": (I, [P, I, P, P]),
+    "orbm_initializer_ransac": (I, [I, P, I, F, I, P, P, P, P]),
     "orbm_compute_distinctive_descriptors": (I, [P, P, I, I, P]),
     "orbx_undistort_keypoints": (I, [P, I, P, P, I, I, P]),
     "orbx_selftest_sincos": (I, [P, I, P, P]),
@@ -847,6 +859,42 @@ def search_for_initialization(pairs, window_size=100, nnratio=0.9, check_ori=Tru
         return [(m, pv, int(nm[p]), int(resc[p])) for p, (m, pv) in enumerate(out)]
     _check(_lib.orbm_search_for_initialization(*args), "orbm_search_for_initialization")
     return [(m, pv, int(nm[p])) for p, (m, pv) in enumerate(out)]
+
+
+def initializer_ransac(pairs, nit, sigma=1.0, device=0):
+    """Initializer::FindHomography / FindFundamental (orbm_initializer_ransac),
+    batched over pairs: dict(keys1 KEYPOINT_DTYPE[n1], keys2 KEYPOINT_DTYPE[n2],
+    match12 int32[n1] as search_for_initialization returns it, sets int32[nit,
+    8] indices into the match list, the rows with match12 >= 0 in ascending
+    order).  Returns per pair dict(H21, F21 float32[3, 3], SH, SF, RH float32,
+    it_H, it_F (-1: no winner, the matrix zero), nmatch, inliers_H, inliers_F
+    uint8[nmatch])."""
+    npair = len(pairs)
+    arr = (RansacPair * max(npair, 1))()
+    keep, off = [], [0]
+    for p, pair in enumerate(pairs):
+        k1 = np.ascontiguousarray(pair["keys1"], KEYPOINT_DTYPE).reshape(-1)
+        k2 = np.ascontiguousarray(pair["keys2"], KEYPOINT_DTYPE).reshape(-1)
+        m12 = np.ascontiguousarray(pair["match12"], np.int32).reshape(-1)
+        sets = np.ascontiguousarray(pair["sets"], np.int32).reshape(-1)
+        if len(m12) != len(k1) or len(sets) < 8 * nit:
+            raise OrbxError(ERR_ARG, "initializer_ransac: match12 needs a row per key of frame 1, sets 8 per iteration")
+        keep.append((k1, k2, m12, sets))
+        arr[p] = RansacPair(len(k1), len(k2), _p(k1), _p(k2), _p(m12), _p(sets))
+        off.append(off[-1] + int((m12 >= 0).sum()))
+    res = np.zeros(max(npair, 1), RANSAC_RESULT_DTYPE)
+    inl_off = np.array(off, np.int32)
+    inl_h = np.zeros(max(off[-1], 1), np.uint8)
+    inl_f = np.zeros(max(off[-1], 1), np.uint8)
+    _check(_lib.orbm_initializer_ransac(npair, ctypes.cast(arr, ctypes.c_void_p), int(nit), float(sigma), device,
+                                        _p(res), _p(inl_h), _p(inl_f), _p(inl_off)), "orbm_initializer_ransac")
+    out = []
+    for p in range(npair):
+        r = res[p]
+        out.append(dict(H21=r["H21"].copy(), F21=r["F21"].copy(), SH=r["SH"], SF=r["SF"], RH=r["RH"],
+                        it_H=int(r["it_H"]), it_F=int(r["it_F"]), nmatch=int(r["nmatch"]),
+                        inliers_H=inl_h[off[p]:off[p + 1]].copy(), inliers_F=inl_f[off[p]:off[p + 1]].copy()))
+    return out
 
 
 def descriptor_distance_batch(a, b, ia, ib, device=0):
