@@ -1027,6 +1027,65 @@ int orbm_initializer_ransac(int npair, const orbx_ransac_pair* pairs, int nit, f
                             uint8_t* inliers_H, uint8_t* inliers_F, const int32_t* inl_off /* npair + 1 */);
 
 /* ---------------------------------------------------------------------------
+ * Initializer::ReconstructH / ReconstructF (src/Initializer.cc:406-864),
+ * batched over frame pairs: the 8 or 4 pose candidates of the
+ * chosen model, CheckRT of every inlier match under each (Triangulate, the
+ * depth, reprojection and parallax tests), the reference's decision, R21, t21
+ * and the winner's points.  Together with orbm_initializer_ransac this is
+ * Initialize (:16-77) from the match list on.  The SVD, the determinant, the
+ * norms, the products and acos are this library's own fixed forms (DESIGN §21,
+ * "unpinned"), not OpenCV's or libm's.
+ * ------------------------------------------------------------------------- */
+#define ORBX_RECON_H 0    /* ReconstructH from ransac->H21 and inliers_H */
+#define ORBX_RECON_F 1    /* ReconstructF from ransac->F21 and inliers_F */
+#define ORBX_RECON_AUTO 2 /* H when ransac->RH > 0.40 (:73), else F */
+
+typedef struct {
+  int n1, n2;
+  const orbx_keypoint* keys1;        /* as in orbx_ransac_pair */
+  const orbx_keypoint* keys2;
+  const int32_t* match12;            /* n1 */
+  float K[9];                        /* row-major calibration matrix (mK) */
+  int32_t model;                     /* ORBX_RECON_* */
+  const orbx_ransac_result* ransac;  /* one record, as orbm_initializer_ransac left it */
+  const uint8_t* inliers_H;          /* ransac->nmatch flags each, match-list order; */
+  const uint8_t* inliers_F;          /* under a forced model the other may be NULL */
+} orbx_recon_pair;
+
+typedef struct {
+  int32_t ok;                        /* the reference's return value */
+  int32_t model_used;                /* ORBX_RECON_H or ORBX_RECON_F */
+  float R21[9], t21[3];              /* row-major; zeros when !ok */
+  int32_t best;                      /* the winning candidate; ReconstructH's bestSolutionIdx
+                                        even when it then fails; -1 for none */
+  int32_t ncand;                     /* 8 (H), 4 (F), 0 (ReconstructH's singular-value exit or
+                                        an absent model) */
+  int32_t nGood[8];                  /* CheckRT's return per candidate; 0 past ncand */
+  float parallax[8];                 /* CheckRT's parallax in degrees; 0 past ncand */
+  int32_t n_inliers;                 /* N: the set flags of the model used */
+} orbx_recon_result;
+
+/* Host pointers; synchronous; safe from several threads.  P3D receives n1 rows
+ * of 3 floats per pair at 3 * key_off[p] and triangulated n1 flags at
+ * key_off[p], both indexed by the key of frame 1 as vP3D / vbTriangulated are
+ * (key_off has npair + 1 entries; rows past n1 are not written): the point and
+ * flag of every match the winning candidate counts, zeros for a key that is
+ * unmatched, no inlier or not counted.  sigma: the Initializer's (th2 = 4 sigma^2);
+ * min_parallax in degrees and min_triangulated as Initialize passes them (1.0,
+ * 50).  When ok == 0, R21, t21 and the pair's P3D rows and flags are zero and
+ * the diagnostics (best, ncand, nGood, parallax, n_inliers) are still filled; a
+ * model whose matrix is absent (it_H / it_F < 0) gives ok = 0 with ncand = 0.
+ * npair == 0 is valid.  ORBX_ERR_ARG, with no output written, for npair < 0, a
+ * required pointer that is NULL (under ORBX_RECON_AUTO both flag arrays are
+ * required), a non-finite entry of K, sigma, min_parallax or key coordinate, a
+ * match12 entry >= n2, a model outside ORBX_RECON_*, ransac->nmatch different
+ * from the count of match12[i] >= 0, or key_off[p] < 0 or key_off[p + 1] -
+ * key_off[p] < n1; ORBX_ERR_UNSUPPORTED for n1 or n2 > 8192 or npair > 65535. */
+int orbm_initializer_reconstruct(int npair, const orbx_recon_pair* pairs, float sigma, float min_parallax,
+                                 int min_triangulated, int device, orbx_recon_result* res, float* P3D,
+                                 uint8_t* triangulated, const int32_t* key_off /* npair + 1 */);
+
+/* ---------------------------------------------------------------------------
  * SURVEY.md §8f rank 4.
  * ------------------------------------------------------------------------- */
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:222-271), batched

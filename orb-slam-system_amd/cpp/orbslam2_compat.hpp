@@ -71,6 +71,14 @@ typedef Point_<float> Point2f;
 typedef Point_<int> Point2i;
 typedef Point2i Point;
 
+template <typename T>
+struct Point3_ {
+  T x = 0, y = 0, z = 0;
+  Point3_() {}
+  Point3_(T x_, T y_, T z_) : x(x_), y(y_), z(z_) {}
+};
+typedef Point3_<float> Point3f;
+
 // cv::KeyPoint: 28 bytes, the field order orbx_keypoint mirrors
 struct KeyPoint {
   Point2f pt;
@@ -1748,15 +1756,15 @@ class Optimizer {
   }
 };
 
-// Initializer (include/Initializer.h, src/Initializer.cc) up to the choice of
-// the model, on the device (orbm_initializer_ransac): the
-// reference's constructor, the match list and index draw of Initialize
-// (:19-63, SetMatches here), and FindHomography / FindFundamental with the
-// reference's signatures.  Initialize itself is not provided: ReconstructH /
-// ReconstructF (:406-865) stay with the caller, who takes RH() and the winning
-// model's matrix and flags there (INTEGRATION.md has the call site).  One
-// device call computes both models; the two Find* members share its result, so
-// the reference's two threads (:68-71) may call them concurrently.  FR: the
+// Initializer (include/Initializer.h, src/Initializer.cc) on the device
+// (orbm_initializer_ransac, orbm_initializer_reconstruct):
+// the reference's constructor, the match list and index draw of Initialize
+// (:19-63, SetMatches here), FindHomography / FindFundamental, ReconstructH /
+// ReconstructF and Initialize with the reference's signatures, and a static
+// Initialize over several initializers that makes one device call for the
+// models and one for the reconstruction of all of them.  One device call
+// computes both models; the two Find* members share its result, so the
+// reference's two threads (:68-71) may call them concurrently.  FR: the
 // reference's Frame -- reads mK and mvKeysUn.
 class Initializer {
  public:
@@ -1888,6 +1896,82 @@ class Initializer {
     }
   }
 
+  // :406-490 and :493-651 on the matches of the last SetMatches.  On false R21
+  // and t21 are released (ReconstructF's :436-437; ReconstructH leaves them in
+  // the reference, where Initialize hands in fresh matrices) and vP3D /
+  // vbTriangulated are left as they were
+  bool ReconstructF(std::vector<bool>& vbMatchesInliers, cv::Mat& F21, cv::Mat& K, cv::Mat& R21, cv::Mat& t21,
+                    std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated, float minParallax,
+                    int minTriangulated, int device = 0) {
+    return ReconstructOne(ORBX_RECON_F, vbMatchesInliers, F21, K, R21, t21, vP3D, vbTriangulated, minParallax,
+                          minTriangulated, device);
+  }
+  bool ReconstructH(std::vector<bool>& vbMatchesInliers, cv::Mat& H21, cv::Mat& K, cv::Mat& R21, cv::Mat& t21,
+                    std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated, float minParallax,
+                    int minTriangulated, int device = 0) {
+    return ReconstructOne(ORBX_RECON_H, vbMatchesInliers, H21, K, R21, t21, vP3D, vbTriangulated, minParallax,
+                          minTriangulated, device);
+  }
+
+  // :16-77: SetMatches, both models, the choice of :73 and the reconstruction
+  // with minParallax = 1.0 and minTriangulated = 50
+  template <class FR>
+  bool Initialize(const FR& CurrentFrame, const std::vector<int>& vMatches12, cv::Mat& R21, cv::Mat& t21,
+                  std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated, int device = 0) {
+    std::vector<cv::Mat> vR(1), vt(1);
+    std::vector<std::vector<cv::Point3f> > vvP(1);
+    std::vector<std::vector<bool> > vvT(1);
+    vvP[0].swap(vP3D);
+    vvT[0].swap(vbTriangulated);
+    const std::vector<bool> ok =
+        Initialize(std::vector<Initializer*>(1, this), std::vector<const FR*>(1, &CurrentFrame),
+                   std::vector<const std::vector<int>*>(1, &vMatches12), vR, vt, vvP, vvT, device);
+    vvP[0].swap(vP3D);
+    vvT[0].swap(vbTriangulated);
+    R21 = vR[0];
+    t21 = vt[0];
+    return ok[0];
+  }
+
+  // Initialize of several initializers: one orbm_initializer_ransac call and one
+  // orbm_initializer_reconstruct call for all of them.  The vectors are resized
+  // to vpInit.size(); entry p is written as the single form writes its
+  // arguments.  All must share sigma and the iteration count
+  template <class FR>
+  static std::vector<bool> Initialize(const std::vector<Initializer*>& vpInit, const std::vector<const FR*>& vpFrames,
+                                      const std::vector<const std::vector<int>*>& vpMatches12,
+                                      std::vector<cv::Mat>& vR21, std::vector<cv::Mat>& vt21,
+                                      std::vector<std::vector<cv::Point3f> >& vvP3D,
+                                      std::vector<std::vector<bool> >& vvbTriangulated, int device = 0) {
+    const size_t n = vpInit.size();
+    if (vpFrames.size() != n || vpMatches12.size() != n) orbx_throw(ORBX_ERR_ARG, "Initializer::Initialize");
+    vR21.resize(n);
+    vt21.resize(n);
+    vvP3D.resize(n);
+    vvbTriangulated.resize(n);
+    if (n == 0) return std::vector<bool>();
+    for (size_t p = 0; p < n; ++p) vpInit[p]->SetMatches(*vpFrames[p], *vpMatches12[p]);
+    FindModels(vpInit, device);
+    std::vector<ReconJob> jobs(n);
+    for (size_t p = 0; p < n; ++p) {
+      Initializer& I = *vpInit[p];
+      std::lock_guard<std::mutex> lk(I.mMutex);
+      jobs[p].init = &I;
+      jobs[p].model = ORBX_RECON_AUTO;
+      jobs[p].ransac = I.mResult;
+      jobs[p].inlH = I.mvInliersH;
+      jobs[p].inlF = I.mvInliersF;
+      MatTo9(I.mK, jobs[p].K);
+    }
+    Reconstruct(jobs, vpInit[0]->mSigma, 1.0f, 50, device);
+    std::vector<bool> ok(n);
+    for (size_t p = 0; p < n; ++p) ok[p] = Deliver(jobs[p], vR21[p], vt21[p], vvP3D[p], vvbTriangulated[p]);
+    return ok;
+  }
+
+  // the record of the last reconstruction through this object (diagnostics)
+  const orbx_recon_result& ReconResult() const { return mRecon; }
+
   // the reference's members (include/Initializer.h:60-80)
   std::vector<cv::KeyPoint> mvKeys1, mvKeys2;
   std::vector<Match> mvMatches12;
@@ -1918,6 +2002,112 @@ class Initializer {
       for (int c = 0; c < 3; ++c) M21.at<float>(r, c) = M[3 * r + c];
   }
 
+  struct ReconJob {
+    Initializer* init = nullptr;
+    int model = ORBX_RECON_AUTO;
+    orbx_ransac_result ransac;
+    std::vector<uint8_t> inlH, inlF;
+    float K[9];
+    orbx_recon_result res;
+    std::vector<float> P3D;
+    std::vector<uint8_t> tri;
+  };
+  static void MatTo9(const cv::Mat& M, float out[9]) {
+    if (M.rows != 3 || M.cols != 3 || M.type() != CV_32F) orbx_throw(ORBX_ERR_ARG, "Initializer: a 3x3 CV_32F matrix");
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) out[3 * r + c] = M.at<float>(r, c);
+  }
+  // one device call for all jobs
+  static void Reconstruct(std::vector<ReconJob>& jobs, float sigma, float minParallax, int minTriangulated,
+                          int device) {
+    const size_t n = jobs.size();
+    std::vector<orbx_recon_pair> pairs(n);
+    std::vector<int32_t> off(n + 1, 0);
+    for (size_t p = 0; p < n; ++p) {
+      Initializer& I = *jobs[p].init;
+      if (I.mSigma != sigma || I.mvIniMatches.size() != I.mvKeys1.size())
+        orbx_throw(ORBX_ERR_ARG, "Initializer::Reconstruct");
+      orbx_recon_pair& P = pairs[p];
+      P.n1 = (int)I.mvKeys1.size();
+      P.n2 = (int)I.mvKeys2.size();
+      P.keys1 = reinterpret_cast<const orbx_keypoint*>(I.mvKeys1.data());
+      P.keys2 = reinterpret_cast<const orbx_keypoint*>(I.mvKeys2.data());
+      P.match12 = I.mvIniMatches.data();
+      for (int e = 0; e < 9; ++e) P.K[e] = jobs[p].K[e];
+      P.model = jobs[p].model;
+      P.ransac = &jobs[p].ransac;
+      // an empty vector still hands over a pointer: a pair may have no match
+      jobs[p].inlH.reserve(1);
+      jobs[p].inlF.reserve(1);
+      P.inliers_H = jobs[p].model == ORBX_RECON_F ? nullptr : jobs[p].inlH.data();
+      P.inliers_F = jobs[p].model == ORBX_RECON_H ? nullptr : jobs[p].inlF.data();
+      off[p + 1] = off[p] + P.n1;
+    }
+    std::vector<orbx_recon_result> res(n);
+    std::vector<float> P3D((size_t)off[n] * 3 + 3);
+    std::vector<uint8_t> tri((size_t)off[n] + 1);
+    orbx_throw(orbm_initializer_reconstruct((int)n, pairs.data(), sigma, minParallax, minTriangulated, device,
+                                            res.data(), P3D.data(), tri.data(), off.data()),
+               "Initializer::Reconstruct");
+    for (size_t p = 0; p < n; ++p) {
+      jobs[p].res = res[p];
+      jobs[p].P3D.assign(P3D.begin() + 3 * (size_t)off[p], P3D.begin() + 3 * (size_t)off[p + 1]);
+      jobs[p].tri.assign(tri.begin() + off[p], tri.begin() + off[p + 1]);
+      std::lock_guard<std::mutex> lk(jobs[p].init->mMutex);
+      jobs[p].init->mRecon = res[p];
+    }
+  }
+  // the outputs of one job as the reference's Reconstruct* leaves them
+  static bool Deliver(const ReconJob& J, cv::Mat& R21, cv::Mat& t21, std::vector<cv::Point3f>& vP3D,
+                      std::vector<bool>& vbTriangulated) {
+    if (!J.res.ok) {
+      R21 = cv::Mat();
+      t21 = cv::Mat();
+      return false;
+    }
+    cv::Mat R(3, 3, CV_32F), t(3, 1, CV_32F);
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) R.at<float>(r, c) = J.res.R21[3 * r + c];
+      t.at<float>(r, 0) = J.res.t21[r];
+    }
+    R21 = R;
+    t21 = t;
+    const size_t n1 = J.tri.size();
+    vP3D.resize(n1);
+    vbTriangulated.assign(n1, false);
+    for (size_t i = 0; i < n1; ++i) {
+      vP3D[i] = cv::Point3f(J.P3D[3 * i], J.P3D[3 * i + 1], J.P3D[3 * i + 2]);
+      vbTriangulated[i] = J.tri[i] != 0;
+    }
+    return true;
+  }
+  bool ReconstructOne(int model, std::vector<bool>& vbMatchesInliers, cv::Mat& M21, cv::Mat& K, cv::Mat& R21,
+                      cv::Mat& t21, std::vector<cv::Point3f>& vP3D, std::vector<bool>& vbTriangulated,
+                      float minParallax, int minTriangulated, int device) {
+    std::vector<ReconJob> jobs(1);
+    ReconJob& J = jobs[0];
+    {
+      std::lock_guard<std::mutex> lk(mMutex);
+      if (vbMatchesInliers.size() != mvMatches12.size()) orbx_throw(ORBX_ERR_ARG, "Initializer: a flag per match");
+      J.init = this;
+      J.model = model;
+      memset(&J.ransac, 0, sizeof J.ransac);
+      J.ransac.it_H = J.ransac.it_F = -1;
+      J.ransac.nmatch = (int32_t)mvMatches12.size();
+      std::vector<uint8_t>& fl = model == ORBX_RECON_H ? J.inlH : J.inlF;
+      fl.resize(vbMatchesInliers.size());
+      for (size_t i = 0; i < fl.size(); ++i) fl[i] = vbMatchesInliers[i] ? 1 : 0;
+      if (!M21.empty()) {  // an empty matrix is the absent model: false without a candidate
+        MatTo9(M21, model == ORBX_RECON_H ? J.ransac.H21 : J.ransac.F21);
+        (model == ORBX_RECON_H ? J.ransac.it_H : J.ransac.it_F) = 0;
+      }
+      MatTo9(K, J.K);
+    }
+    Reconstruct(jobs, mSigma, minParallax, minTriangulated, device);
+    return Deliver(J, R21, t21, vP3D, vbTriangulated);
+  }
+
+  orbx_recon_result mRecon = orbx_recon_result();
   std::vector<int32_t> mvIniMatches;  // vMatches12 as given: the ABI's match12
   std::mutex mMutex, mComputeMutex;
   bool mbComputed = false;

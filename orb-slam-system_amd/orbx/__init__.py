@@ -74,7 +74,7 @@ EXPORTED = [
     "orbm_keyframe_project", "orbm_kf_plan_create", "orbm_kf_plan_destroy", "orbm_kf_plan_search",
     "orbm_kf_plan_project", "orbm_kf_plan_project_search",
     "orbm_pose_optimization", "orbm_pose_plan_create", "orbm_pose_plan_destroy", "orbm_pose_plan_optimize",
-    "orbm_initializer_ransac",
+    "orbm_initializer_ransac", "orbm_initializer_reconstruct",
 ]
 
 
@@ -237,6 +237,19 @@ RANSAC_RESULT_DTYPE = np.dtype([("H21", "<f4", (3, 3)), ("F21", "<f4", (3, 3)), 
                                 ("RH", "<f4"), ("it_H", "<i4"), ("it_F", "<i4"), ("nmatch", "<i4")])
 
 
+class ReconPair(ctypes.Structure):  # orbx_recon_pair
+    _fields_ = [("n1", ctypes.c_int), ("n2", ctypes.c_int), ("keys1", ctypes.c_void_p), ("keys2", ctypes.c_void_p),
+                ("match12", ctypes.c_void_p), ("K", ctypes.c_float * 9), ("model", ctypes.c_int32),
+                ("ransac", ctypes.c_void_p), ("inliers_H", ctypes.c_void_p), ("inliers_F", ctypes.c_void_p)]
+
+
+# orbx_recon_result
+RECON_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("model_used", "<i4"), ("R21", "<f4", (3, 3)), ("t21", "<f4", (3,)),
+                               ("best", "<i4"), ("ncand", "<i4"), ("nGood", "<i4", (8,)), ("parallax", "<f4", (8,)),
+                               ("n_inliers", "<i4")])
+RECON_H, RECON_F, RECON_AUTO = 0, 1, 2  # ORBX_RECON_*
+
+
 # k_init_cand's list length per row and the feature limit (csrc/init_internal.h)
 INIT_T, INIT_MAXN = 8, 8192
 
@@ -340,6 +353,7 @@ _sig = {
     "orbm_pose_plan_destroy": (I, [P]),
     "orbm_pose_plan_optimize": (I, [P, I, P, P]),
     "orbm_initializer_ransac": (I, [I, P, I, F, I, P, P, P, P]),
+    "orbm_initializer_reconstruct": (I, [I, P, F, F, I, I, P, P, P, P]),
     "orbm_compute_distinctive_descriptors": (I, [P, P, I, I, P]),
     "orbx_undistort_keypoints": (I, [P, I, P, P, I, I, P]),
     "orbx_selftest_sincos": (I, [P, I, P, P]),
@@ -894,6 +908,74 @@ def initializer_ransac(pairs, nit, sigma=1.0, device=0):
         out.append(dict(H21=r["H21"].copy(), F21=r["F21"].copy(), SH=r["SH"], SF=r["SF"], RH=r["RH"],
                         it_H=int(r["it_H"]), it_F=int(r["it_F"]), nmatch=int(r["nmatch"]),
                         inliers_H=inl_h[off[p]:off[p + 1]].copy(), inliers_F=inl_f[off[p]:off[p + 1]].copy()))
+    return out
+
+
+def ransac_record(r):
+    """one orbx_ransac_result record from a dict as initializer_ransac returns it
+    (or from a RANSAC_RESULT_DTYPE record, passed through)"""
+    if isinstance(r, np.ndarray) or isinstance(r, np.void):
+        return np.ascontiguousarray(r, RANSAC_RESULT_DTYPE).reshape(())
+    rec = np.zeros((), RANSAC_RESULT_DTYPE)
+    for k in RANSAC_RESULT_DTYPE.names:
+        rec[k] = r[k]
+    return rec
+
+
+def initializer_reconstruct(pairs, sigma=1.0, min_parallax=1.0, min_triangulated=50, device=0):
+    """Initializer::ReconstructH / ReconstructF (orbm_initializer_reconstruct),
+    batched over pairs: dict(keys1 KEYPOINT_DTYPE[n1], keys2 KEYPOINT_DTYPE[n2],
+    match12 int32[n1], K float32[3, 3], model RECON_H / RECON_F / RECON_AUTO
+    (default AUTO: H when RH > 0.40), ransac: the pair's result of
+    initializer_ransac (its dict, or a RANSAC_RESULT_DTYPE record), inliers_H,
+    inliers_F uint8[nmatch]; under a forced model the other may be None or
+    missing; a dict ransac supplies them when they are not given).  Returns per
+    pair dict(ok, model_used, R21 float32[3, 3], t21 float32[3], best, ncand,
+    nGood int32[8], parallax float32[8], n_inliers, P3D float32[n1, 3],
+    triangulated uint8[n1]); R21, t21, P3D and triangulated are zero when not
+    ok."""
+    npair = len(pairs)
+    arr = (ReconPair * max(npair, 1))()
+    keep, off = [], [0]
+    for p, pair in enumerate(pairs):
+        k1 = np.ascontiguousarray(pair["keys1"], KEYPOINT_DTYPE).reshape(-1)
+        k2 = np.ascontiguousarray(pair["keys2"], KEYPOINT_DTYPE).reshape(-1)
+        m12 = np.ascontiguousarray(pair["match12"], np.int32).reshape(-1)
+        K = np.ascontiguousarray(pair["K"], np.float32).reshape(-1)
+        if len(m12) != len(k1) or len(K) != 9:
+            raise OrbxError(ERR_ARG, "initializer_reconstruct: match12 needs a row per key of frame 1, K nine entries")
+        rs = pair["ransac"]
+        rec = ransac_record(rs)
+        nm = int((m12 >= 0).sum())
+        fl = []
+        for name in ("inliers_H", "inliers_F"):
+            f = pair.get(name)
+            if f is None and isinstance(rs, dict):
+                f = rs.get(name)
+            if f is not None:
+                f = np.ascontiguousarray(f, np.uint8).reshape(-1)
+                if len(f) < nm:
+                    raise OrbxError(ERR_ARG, "initializer_reconstruct: a flag per entry of the match list")
+            fl.append(f)
+        keep.append((k1, k2, m12, rec, fl))
+        arr[p] = ReconPair(len(k1), len(k2), _p(k1), _p(k2), _p(m12), (ctypes.c_float * 9)(*K.tolist()),
+                           int(pair.get("model", RECON_AUTO)), _p(rec), None if fl[0] is None else _p(fl[0]),
+                           None if fl[1] is None else _p(fl[1]))
+        off.append(off[-1] + len(k1))
+    res = np.zeros(max(npair, 1), RECON_RESULT_DTYPE)
+    key_off = np.array(off, np.int32)
+    p3d = np.zeros((max(off[-1], 1), 3), np.float32)
+    tri = np.zeros(max(off[-1], 1), np.uint8)
+    _check(_lib.orbm_initializer_reconstruct(npair, ctypes.cast(arr, ctypes.c_void_p), float(sigma),
+                                             float(min_parallax), int(min_triangulated), device, _p(res), _p(p3d),
+                                             _p(tri), _p(key_off)), "orbm_initializer_reconstruct")
+    out = []
+    for p in range(npair):
+        r = res[p]
+        out.append(dict(ok=int(r["ok"]), model_used=int(r["model_used"]), R21=r["R21"].copy(), t21=r["t21"].copy(),
+                        best=int(r["best"]), ncand=int(r["ncand"]), nGood=r["nGood"].copy(),
+                        parallax=r["parallax"].copy(), n_inliers=int(r["n_inliers"]),
+                        P3D=p3d[off[p]:off[p + 1]].copy(), triangulated=tri[off[p]:off[p + 1]].copy()))
     return out
 
 
