@@ -230,7 +230,13 @@ int orbx_debug_fail_acquire(int nth);
  *                          the descriptors sample it (k_orient_brief_lb);
  *   ORBX_PLAN_FAST_DENSE   every FAST strip takes the dense post-pass, as
  *                          before the per-strip choice (DESIGN.md §4 round 7;
- *                          for A/B timing and tests).
+ *                          for A/B timing and tests);
+ *   ORBX_PLAN_NO_TWINS     a keypoint that wins the quadtree both in a level
+ *                          and in a level aliasing it (level 1 of the
+ *                          reference's scale table is level 0's image) is
+ *                          computed once per level, as before DESIGN.md §4
+ *                          round 10; by default it is computed once and
+ *                          written to both rows (for A/B timing and tests).
  * Automatic (0): the tile pyramid, and the level blur when nfeatures x 43 x
  * 48 exceeds ORBX_LB_RATIO x the unique level pixels.
  * The round-4 row-streaming pyramid and fused pyramid + FAST kernels (flags
@@ -241,6 +247,7 @@ int orbx_debug_fail_acquire(int nth);
 #define ORBX_PLAN_BRIEF_PATCH 8
 #define ORBX_PLAN_BRIEF_LEVEL 16
 #define ORBX_PLAN_FAST_DENSE 64
+#define ORBX_PLAN_NO_TWINS 128
 int orbx_plan_set_options(orbx_plan* plan, int flags);
 
 /* mvImagePyramid[level] of frame `frame` of the last orbx_plan_extract on

@@ -30,22 +30,40 @@ __global__ void k_fast_strips_p288(const uint8_t*, size_t, size_t, const uint8_t
                               size_t, uint32_t*, int, int, int, int, int, int, int, int*, int, int);
 __global__ void k_quadtree(const LevelInfo*, const CellInfo*, const uint32_t*, size_t,
                            const uint32_t*, int, uint32_t*, int32_t*, size_t, uint32_t*, size_t,
-                           int*, int, int, int, int*, uint32_t*);
+                           int*, int, int, int, int*, uint32_t*, int*, uint32_t*, uint32_t*, size_t);
+__global__ void k_quadtree_tw(const LevelInfo*, const CellInfo*, const uint32_t*, size_t,
+                           const uint32_t*, int, uint32_t*, int32_t*, size_t, uint32_t*, size_t,
+                           int*, int, int, int, int*, uint32_t*, int*, uint32_t*, uint32_t*, size_t);
 __global__ void k_quadtree_j6(const LevelInfo*, const CellInfo*, const uint32_t*, size_t,
                               const uint32_t*, int, uint32_t*, int32_t*, size_t, uint32_t*, size_t,
-                              int*, int, int, int, int*, uint32_t*);
+                              int*, int, int, int, int*, uint32_t*, int*, uint32_t*, uint32_t*, size_t);
+__global__ void k_quadtree_j6_tw(const LevelInfo*, const CellInfo*, const uint32_t*, size_t,
+                              const uint32_t*, int, uint32_t*, int32_t*, size_t, uint32_t*, size_t,
+                              int*, int, int, int, int*, uint32_t*, int*, uint32_t*, uint32_t*, size_t);
 __global__ void k_pack_results(const int*, const int*, const uint4*, const uint4*, int, uint4*, uint32_t);
 static_assert(sizeof(orbx_keypoint) == 28, "k_pack_results copies 7-dword keypoint rows");
 __global__ void k_quadtree_wide(const LevelInfo*, const CellInfo*, const uint32_t*, size_t,
                                 const uint32_t*, int, uint32_t*, int32_t*, size_t, uint32_t*, size_t,
-                                int*, int, int, int, int*, uint32_t*);
+                                int*, int, int, int, int*, uint32_t*, int*, uint32_t*, uint32_t*, size_t);
+__global__ void k_quadtree_wide_tw(const LevelInfo*, const CellInfo*, const uint32_t*, size_t,
+                                const uint32_t*, int, uint32_t*, int32_t*, size_t, uint32_t*, size_t,
+                                int*, int, int, int, int*, uint32_t*, int*, uint32_t*, uint32_t*, size_t);
 __global__ void k_orient_brief(const uint8_t*, size_t, size_t, const uint8_t*, size_t,
                                const BriefArgs, const uint32_t*, size_t, const int*,
-                               orbx_keypoint*, uint8_t*, int*, const uint32_t*, int);
+                               orbx_keypoint*, uint8_t*, int*, const uint32_t*, int, const int*,
+                               const uint32_t*, const uint32_t*, size_t);
+__global__ void k_orient_brief_tw(const uint8_t*, size_t, size_t, const uint8_t*, size_t,
+                               const BriefArgs, const uint32_t*, size_t, const int*,
+                               orbx_keypoint*, uint8_t*, int*, const uint32_t*, int, const int*,
+                               const uint32_t*, const uint32_t*, size_t);
 __global__ void k_orient_brief_lb(const uint8_t*, size_t, size_t, const uint8_t*, size_t,
                                   const BriefArgs, const uint32_t*, size_t, const int*,
-                                  orbx_keypoint*, uint8_t*, int*, const uint32_t*, int,
-                                  const uint8_t*, size_t);
+                                  orbx_keypoint*, uint8_t*, int*, const uint32_t*, int, const int*,
+                                  const uint32_t*, const uint32_t*, size_t, const uint8_t*, size_t);
+__global__ void k_orient_brief_lb_tw(const uint8_t*, size_t, size_t, const uint8_t*, size_t,
+                                  const BriefArgs, const uint32_t*, size_t, const int*,
+                                  orbx_keypoint*, uint8_t*, int*, const uint32_t*, int, const int*,
+                                  const uint32_t*, const uint32_t*, size_t, const uint8_t*, size_t);
 __global__ void k_blur(const uint8_t*, size_t, size_t, const uint8_t*, size_t, uint8_t*, size_t, const BlurArgs);
 __global__ void k_synth(uint8_t*, int, int, size_t, int, int);
 __global__ void k_selftest_sincos(const float*, int, float*);
@@ -187,6 +205,9 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
   if (set_max_dynamic_lds((const void*)k_quadtree, device) ||
       set_max_dynamic_lds((const void*)k_quadtree_j6, device) ||
       set_max_dynamic_lds((const void*)k_quadtree_wide, device) ||
+      set_max_dynamic_lds((const void*)k_quadtree_tw, device) ||
+      set_max_dynamic_lds((const void*)k_quadtree_j6_tw, device) ||
+      set_max_dynamic_lds((const void*)k_quadtree_wide_tw, device) ||
       set_max_dynamic_lds((const void*)k_fast_strips, device) ||
       set_max_dynamic_lds((const void*)k_fast_strips_p288, device) ||
       set_max_dynamic_lds((const void*)k_pyramid, device)) return ORBX_ERR_HIP;
@@ -248,6 +269,7 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
     p->bargs.patch[l] = lv.patch_size;
     p->bargs.bpitch[l] = lv.bpitch;
     p->bargs.blur_off[l] = lv.blur_off;
+    p->bargs.twin[l] = -1; /* the pairs are set per launch (extract_pass) */
   }
   // level-blur mode (k_blur + k_orient_brief_lb): blur every unique level
   // once when the keypoints' per-keypoint patches (43 x 48 px each) would
@@ -365,13 +387,23 @@ extern "C" int orbx_plan_create(const orbx_params* prm, int width, int height, i
   p->slot_stride = round_up((size_t)P.nslots, 64);
   p->qk_stride = round_up((size_t)P.qk_elems, 64);
   p->qout_stride = round_up((size_t)P.kcap, 64);
+  p->tw_stride = round_up((size_t)P.tw_words, 64);
   const size_t B = (size_t)max_batch;
+  // twin rows (LevelInfo::twin): plans with an alias level keep the winners'
+  // key indices, the pairs' bitmaps and the per-level flags behind qperm, in
+  // the same allocation
+  const size_t tw_elems = P.tw_words > 0 ? B * (p->qout_stride + p->tw_stride + round_up((size_t)P.params.nlevels, 64)) : 0;
   if (p->d_pyr.alloc(B * p->pyr_stride) || p->d_slots.alloc(B * p->slot_stride) ||
       p->d_ccount.alloc(B * (size_t)(P.ncells ? P.ncells : 1)) || p->d_qkeys.alloc(B * p->qk_stride) ||
       p->d_qnode.alloc(B * p->qk_stride) || p->d_qout.alloc(B * p->qout_stride) ||
-      p->d_qperm.alloc(B * p->qout_stride) || p->d_lcount.alloc(B * (size_t)P.params.nlevels) ||
+      p->d_qperm.alloc(B * p->qout_stride + tw_elems) || p->d_lcount.alloc(B * (size_t)P.params.nlevels) ||
       p->d_err.alloc(4) || p->d_fs_cnt.alloc(FS_CNT_LINES * FS_CNT_STRIDE))
     return ORBX_ERR_HIP;
+  if (tw_elems) {
+    p->d_qkidx = p->d_qperm + B * p->qout_stride;
+    p->d_twscr = p->d_qkidx + B * p->qout_stride;
+    p->d_twvalid = reinterpret_cast<int*>(p->d_twscr + B * p->tw_stride);
+  }
   // stream-ordered: no device-wide synchronisation (other extractors and
   // the matcher may be running on this device from other threads)
   if (hipMemsetAsync(p->d_err, 0, 16, us) != hipSuccess ||
@@ -418,6 +450,20 @@ static int extract_pass(orbx_plan* p, const uint8_t* frames, int n, size_t fstri
   int32_t* const d_qnode = p->d_qnode + f0 * p->qk_stride;
   uint32_t* const d_qout = p->d_qout + f0 * p->qout_stride;
   int* const d_lcount = p->d_lcount + f0 * (size_t)L;
+  // twin rows: a unique level's keypoint also writes the row of its alias
+  // level's winner of the same key, which is then not computed (plans with
+  // an alias level, unless ORBX_PLAN_NO_TWINS); off, no level has a partner
+  // and the kernels take none of the twin buffers
+  const bool twins = p->d_twvalid && !(p->options & ORBX_PLAN_NO_TWINS);
+  int* const d_twvalid = twins ? p->d_twvalid + f0 * (size_t)L : nullptr;
+  uint32_t* const d_qkidx = twins ? p->d_qkidx + f0 * p->qout_stride : nullptr;
+  uint32_t* const d_twscr = twins ? p->d_twscr + f0 * p->tw_stride : nullptr;
+  BriefArgs ba = p->bargs;
+  if (twins)
+    for (int l = 0; l < L; ++l) {
+      ba.twin[l] = P.levels[l].twin;
+      ba.tw_off[l] = P.levels[l].tw_off;
+    }
   // strips [strip0, strip1) of launch group g
   // the call's level-0 alignment (k_fast_strips takes the planner's staging
   // decisions when the frames are 16-B aligned)
@@ -491,11 +537,14 @@ static int extract_pass(orbx_plan* p, const uint8_t* frames, int n, size_t fstri
 #ifdef ORBX_PROFILING
   if (const char* e = getenv("ORBX_DEBUG_QT_WIDE")) qt_wide = atoi(e) != 0 && p->qt_lds_wide <= 150 * 1024;  // A/B (profiling only)
 #endif
-  hipLaunchKernelGGL(qt_wide ? k_quadtree_wide : P.levels[0].w * P.levels[0].h >= (1 << 20) ? k_quadtree : k_quadtree_j6,
+  const bool qt_big = P.levels[0].w * P.levels[0].h >= (1 << 20);
+  hipLaunchKernelGGL(twins ? (qt_wide ? k_quadtree_wide_tw : qt_big ? k_quadtree_tw : k_quadtree_j6_tw)
+                           : (qt_wide ? k_quadtree_wide : qt_big ? k_quadtree : k_quadtree_j6),
                      dim3(n, L), dim3(qt_wide ? 1024 : 256), qt_wide ? p->qt_lds_wide : p->qt_lds, s, p->d_lv, p->d_cells,
                      d_slots, p->slot_stride, d_ccount, P.ncells, d_qkeys, d_qnode,
                      p->qk_stride, d_qout, p->qout_stride, d_lcount, L, P.qt_smax,
-                     P.qt_max_cells, p->d_err, p->d_qperm + f0 * p->qout_stride);
+                     P.qt_max_cells, p->d_err, p->d_qperm + f0 * p->qout_stride, d_twvalid, d_qkidx,
+                     d_twscr, p->tw_stride);
   p->timer.end(ORBX_STAGE_QUADTREE, s);
   // K4+K5+K6+K7 orientation, blur-at-sample descriptors, assembly
   p->timer.begin(ORBX_STAGE_BRIEF, s);
@@ -513,19 +562,26 @@ static int extract_pass(orbx_plan* p, const uint8_t* frames, int n, size_t fstri
   // (tools/obdiv_fetch.sh: ~12 / 6 / 3 / 2 / 1 per wave read 1726 / 1311 /
   // 1091 / 1119 / 1003 MB in 0.544 / 0.551 / 0.576 / 0.599 / 0.653 ms)
   const int ob_full = std::max(4, std::min(P.kcap, P.params.nfeatures + 256));
-  const int ob_kpw = (long long)P.levels[0].w * P.levels[0].h >= (1 << 20) ? 6 : 12;
+  // With twin rows a wave passes over the alias level's twins among its
+  // positions (a third of them on the bench streams, N1 / sum N ~ 18 % on
+  // real frames), so it takes half as many positions again: c4 / c1 / c5
+  // BRIEF 0.346 / 0.609 / 0.535 ms at 6 / 12 / 12 positions per wave, 0.333 /
+  // 0.593 / 0.529 at 9 / 18 / 18
+  const int ob_kpw = ((long long)P.levels[0].w * P.levels[0].h >= (1 << 20) ? 6 : 12) * (twins ? 3 : 2) / 2;
   int ob_waves = std::min(ob_full, std::max((ob_full + ob_kpw - 1) / ob_kpw, (16384 + n - 1) / n));
   if (p->ob_div > 0) ob_waves = std::max(4, ob_full / p->ob_div); /* profiling only */
   if (p->uses_lb()) {
-    hipLaunchKernelGGL(k_orient_brief_lb, dim3((ob_waves + 3) / 4, n),
-                       dim3(256), p->pad_brief, s, frames, fstride, rstride, d_pyr, p->pyr_stride, p->bargs,
+    hipLaunchKernelGGL(twins ? k_orient_brief_lb_tw : k_orient_brief_lb, dim3((ob_waves + 3) / 4, n),
+                       dim3(256), p->pad_brief, s, frames, fstride, rstride, d_pyr, p->pyr_stride, ba,
                        d_qout, p->qout_stride, d_lcount, kps, desc,
-                       counts, p->d_qperm + f0 * p->qout_stride, p->dbg, d_blur, p->blur_stride);
+                       counts, p->d_qperm + f0 * p->qout_stride, p->dbg, d_twvalid, d_qkidx, d_twscr,
+                       p->tw_stride, d_blur, p->blur_stride);
   } else {
-    hipLaunchKernelGGL(k_orient_brief, dim3((ob_waves + 3) / 4, n),
-                       dim3(256), p->pad_brief, s, frames, fstride, rstride, d_pyr, p->pyr_stride, p->bargs,
+    hipLaunchKernelGGL(twins ? k_orient_brief_tw : k_orient_brief, dim3((ob_waves + 3) / 4, n),
+                       dim3(256), p->pad_brief, s, frames, fstride, rstride, d_pyr, p->pyr_stride, ba,
                        d_qout, p->qout_stride, d_lcount, kps, desc,
-                       counts, p->d_qperm + f0 * p->qout_stride, p->dbg);
+                       counts, p->d_qperm + f0 * p->qout_stride, p->dbg, d_twvalid, d_qkidx, d_twscr,
+                       p->tw_stride);
   }
   p->timer.end(ORBX_STAGE_BRIEF, s);
   if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
@@ -577,7 +633,7 @@ extern "C" int orbx_plan_check(orbx_plan* p, void* stream) {
 }
 
 extern "C" int orbx_plan_set_options(orbx_plan* p, int flags) {
-  if (!p || (flags & ~(ORBX_PLAN_PYR_TILES | ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL | ORBX_PLAN_FAST_DENSE)) ||
+  if (!p || (flags & ~(ORBX_PLAN_PYR_TILES | ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL | ORBX_PLAN_FAST_DENSE | ORBX_PLAN_NO_TWINS)) ||
       (flags & (ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL)) == (ORBX_PLAN_BRIEF_PATCH | ORBX_PLAN_BRIEF_LEVEL))
     return ORBX_ERR_ARG;
   if ((flags & ORBX_PLAN_BRIEF_LEVEL) && !p->d_blur) {

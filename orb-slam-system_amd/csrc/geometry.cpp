@@ -615,6 +615,25 @@ int plan_geometry(const orbx_params& p, int width, int height, Plan& P) {
   P.qt_smax = smax;
   P.qt_max_cells = maxc;
   P.geo.kcap = kout;
+  /* twin pairs: each unique level with its first alias level (further
+   * aliases of the same level are computed on their own).  The bitmaps hold
+   * one bit per key index, at most the 3 smax words k_quadtree has LDS for */
+  long long tw = 0;
+  for (int l = 0; l < L; ++l) P.levels[l].twin = -1, P.levels[l].tw_off = P.levels[l].tw_nw = P.levels[l].tw_pad = 0;
+  for (int l = 0; l < L; ++l) {
+    LevelInfo& lv = P.levels[l];
+    if (lv.unique == l || P.levels[lv.unique].twin >= 0) continue;
+    LevelInfo& u = P.levels[lv.unique];
+    const int nw = (int)std::min<long long>(3LL * smax, (u.nslots + 31) / 32);
+    u.twin = l;
+    lv.twin = lv.unique;
+    for (LevelInfo* q : {&u, &lv}) {
+      q->tw_nw = nw;
+      q->tw_off = (int)tw;
+      tw += 2LL * nw;
+    }
+  }
+  P.tw_words = tw;
 
   /* algorithmic bytes of pyramid + FAST per frame: every unique level is
    * written once by the resize that reads its source level, and read once

@@ -52,6 +52,7 @@ struct Plan {
   int ncells = 0, kcap = 0;
   int qt_smax = 0;     /* max DistributeOctTree splittable list length */
   int qt_max_cells = 0;
+  long long tw_words = 0; /* twin scratch per frame (LevelInfo::tw_off), 0: no alias level */
   orbx_geometry geo;
 };
 

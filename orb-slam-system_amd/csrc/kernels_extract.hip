@@ -1313,9 +1313,11 @@ __device__ __forceinline__ int upper_bound_i(const int* a, int n, int v) {
       const uint32_t *__restrict__ ccount, int ncells_total, uint32_t *__restrict__ qkeys, \
       int32_t *__restrict__ qnode, size_t qk_stride, uint32_t *__restrict__ qout,          \
       size_t qout_stride, int *__restrict__ lcount, int nlevels, int smax, int maxcells,   \
-      int *__restrict__ err, uint32_t *__restrict__ qperm
+      int *__restrict__ err, uint32_t *__restrict__ qperm, int *__restrict__ twvalid,      \
+      uint32_t *__restrict__ qkidx, uint32_t *__restrict__ twscr, size_t tw_stride
 #define QT_KERNEL_PASS \
-  lv, cells, slots, slot_stride, ccount, ncells_total, qkeys, qnode, qk_stride, qout, qout_stride, lcount, nlevels, smax, maxcells, err, qperm
+  lv, cells, slots, slot_stride, ccount, ncells_total, qkeys, qnode, qk_stride, qout, qout_stride, lcount, nlevels, smax, maxcells, err, qperm, \
+  twvalid, qkidx, twscr, tw_stride
 
 // QJ: keys per thread held in registers (NT QJ per level; more spill to the
 // global keys/node arrays).  Both instantiations are built for 8 waves per
@@ -1324,7 +1326,9 @@ __device__ __forceinline__ int upper_bound_i(const int* a, int n, int v) {
 // ms per step): 12 keys at 95 VGPRs (5 waves) 0.089 / 0.173 / 0.117 (c4 /
 // c1 / c5); 8 keys at 8 waves 0.089 / 0.123 / 0.078; 6 keys at 8 waves
 // 0.092 / 0.115 / 0.075 -- 8 for 1080p-class levels, 6 below.
-template <int QJ, int NT>
+// TWINS: the plan has an alias pair and twin rows are on (the _tw kernels);
+// without it the twin arguments are never read
+template <int QJ, int NT, bool TWINS>
 __device__ __forceinline__ void qt_body(QT_KERNEL_ARGS) {
   extern __shared__ __align__(16) int smem[];
   // grid (frames, levels): dispatch is round-robin over the 8 XCDs in
@@ -1653,6 +1657,16 @@ __device__ __forceinline__ void qt_body(QT_KERNEL_ARGS) {
   // key index: a bitmap over the key indices and a scan of its popcounts.
   uint32_t* perm = qperm + (size_t)f * qout_stride + L.kout_off;
   const int nw = (C + 31) >> 5;
+  // twin rows (LevelInfo::twin).  A unique level and its alias level ran over
+  // the same key list: key index k wins in both <=> its two output rows
+  // differ in octave / scale only.  Each level of a pair leaves its winners'
+  // bitmap and rank prefix (twscr) and each winner's key index in processing
+  // order (qkidx); k_orient_brief looks a keypoint's index up in the other
+  // level's bitmap: the unique level's keypoint writes both rows, the alias
+  // level's is skipped.  A level without a bitmap (nw > 3 smax: identity
+  // order) is marked invalid and its pair computes everything.
+  const bool paired = TWINS && L.twin >= 0;  // this level has a partner
+  bool tw_valid = false;
 #ifdef OB_NO_PERM  // profiling variant: BRIEF in output order
   if (false) {
 #else
@@ -1670,23 +1684,43 @@ __device__ __forceinline__ void qt_body(QT_KERNEL_ARGS) {
     for (int w = tid; w < nw; w += NT) pc[w] = __popc(bm[w]);
     __syncthreads();
     block_scan_excl<NT>(pc, nw, wtmp);
+    tw_valid = paired && nw <= L.tw_nw;
+    uint32_t* kidx = qkidx + (size_t)f * qout_stride + L.kout_off;
     for (int i = tid; i < newS; i += NT) {
       const uint32_t k = 0xFFFFFFu - (best[i] & 0xFFFFFFu);
-      perm[pc[k >> 5] + __popc(bm[k >> 5] & ((1u << (k & 31)) - 1u))] = (uint32_t)i;
+      const int r = pc[k >> 5] + __popc(bm[k >> 5] & ((1u << (k & 31)) - 1u));
+      perm[r] = (uint32_t)i;
+      if (tw_valid) kidx[r] = k;
+    }
+    if (tw_valid) {
+      uint32_t* gb = twscr + (size_t)f * tw_stride + L.tw_off;  // pairs {bitmap word, winners below it}
+      for (int w = tid; w < nw; w += NT) {
+        gb[2 * w] = bm[w];
+        gb[2 * w + 1] = (uint32_t)pc[w];
+      }
     }
   } else {
     for (int i = tid; i < newS; i += NT) perm[i] = (uint32_t)i;
   }
-  if (tid == 0) lcount[(size_t)f * nlevels + l] = newS;
+  if (tid == 0) {
+    lcount[(size_t)f * nlevels + l] = newS;
+    if (TWINS) twvalid[(size_t)f * nlevels + l] = tw_valid ? 1 : 0;
+  }
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_quadtree(QT_KERNEL_ARGS) {
-  qt_body<8, 256>(QT_KERNEL_PASS);
+  qt_body<8, 256, false>(QT_KERNEL_PASS);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_quadtree_tw(QT_KERNEL_ARGS) {
+  qt_body<8, 256, true>(QT_KERNEL_PASS);
 }
 // single-frame / small-batch calls (a grid of a few workgroups, the level-0
 // one sets the latency): 1024 threads walk the keys and the node lists
 __global__ __launch_bounds__(1024) void k_quadtree_wide(QT_KERNEL_ARGS) {
-  qt_body<8, 1024>(QT_KERNEL_PASS);
+  qt_body<8, 1024, false>(QT_KERNEL_PASS);
+}
+__global__ __launch_bounds__(1024) void k_quadtree_wide_tw(QT_KERNEL_ARGS) {
+  qt_body<8, 1024, true>(QT_KERNEL_PASS);
 }
 #ifndef QT_JSMALL
 #define QT_JSMALL 6 /* keys per thread in registers below 1 Mpx levels */
@@ -1695,7 +1729,10 @@ __global__ __launch_bounds__(1024) void k_quadtree_wide(QT_KERNEL_ARGS) {
 #define QT_WPE_SMALL 8
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_WPE_SMALL))) void k_quadtree_j6(QT_KERNEL_ARGS) {
-  qt_body<QT_JSMALL, 256>(QT_KERNEL_PASS);
+  qt_body<QT_JSMALL, 256, false>(QT_KERNEL_PASS);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QT_WPE_SMALL))) void k_quadtree_j6_tw(QT_KERNEL_ARGS) {
+  qt_body<QT_JSMALL, 256, true>(QT_KERNEL_PASS);
 }
 
 // ---------------------------------------------------------------------------
@@ -1937,6 +1974,8 @@ __device__ __forceinline__ ob_s2 as_s2(uint32_t x) { return __builtin_bit_cast(o
 // lives and where its patch starts (all wave-uniform).
 struct BriefKp {
   int oi;  // output position (levels concatenated, node order within a level)
+  int oi2; // output position of the twin row in the alias level (-1: none)
+  bool skip; // an alias level's twin row: written by its unique level's keypoint (nothing else is set)
   int l, x, y, score, patch_size;
   float scale;
   const uint8_t* img;
@@ -2071,13 +2110,18 @@ __device__ __forceinline__ void brief_commit(const BriefRegs<true>& R, uint32_t*
   const uint8_t *__restrict__ frames, size_t fstride, size_t rstride, const uint8_t *__restrict__ pyr, \
       size_t pstride, const BriefArgs A, const uint32_t *__restrict__ qout, size_t qout_stride,        \
       const int *__restrict__ lcount, orbx_keypoint *__restrict__ kps, uint8_t *__restrict__ desc,     \
-      int *__restrict__ counts, const uint32_t *__restrict__ qperm, int dbg
-#define OB_KERNEL_PASS frames, fstride, rstride, pyr, pstride, A, qout, qout_stride, lcount, kps, desc, counts, qperm, dbg
+      int *__restrict__ counts, const uint32_t *__restrict__ qperm, int dbg,                        \
+      const int *__restrict__ twvalid, const uint32_t *__restrict__ qkidx,                          \
+      const uint32_t *__restrict__ twscr, size_t tw_stride
+#define OB_KERNEL_PASS \
+  frames, fstride, rstride, pyr, pstride, A, qout, qout_stride, lcount, kps, desc, counts, qperm, dbg, twvalid, qkidx, twscr, tw_stride
 // LB = false: per-keypoint blur (the horizontal pass over the staged
 // unblurred patch, the vertical taps at every sample); LB = true: samples
 // read the level k_blur materialised (the planner picks per geometry,
 // Plan::lb)
-template <bool LB>
+// TWINS: twin rows (the _tw kernels: plans with an alias pair, option on);
+// without it this is the kernel of a plan without alias levels
+template <bool LB, bool TWINS>
 __device__ __forceinline__ void ob_body(OB_KERNEL_ARGS, const uint8_t* __restrict__ blur, size_t bstride) {
 #if OB_HPASS == 1
   // guard dwords: the MFMA pass's windows start 2 dwords before a row and its
@@ -2100,8 +2144,16 @@ __device__ __forceinline__ void ob_body(OB_KERNEL_ARGS, const uint8_t* __restric
   const int total = lane_value(incl, 63);  // all lanes active here
   if (bx == 0 && threadIdx.x == 0) counts[f] = total;
   const int excl = incl - lcv;
+  // twin rows (k_quadtree): bit l = level l of this frame left its winners'
+  // bitmap (a scalar mask; 0 with the plan option off)
+  // (the pointer test is redundant in the _tw kernels; as a compile-time
+  // test alone the twin kernels spilled 20-26 VGPRs to scratch, gfx950 / -O3)
+  uint32_t tvmask = 0;
+  if (TWINS && twvalid) tvmask = (uint32_t)__ballot(lane < nlevels && twvalid[(size_t)f * nlevels + min(lane, nlevels - 1)] != 0);
   const uint32_t* Q = qout + (size_t)f * qout_stride;
   const uint32_t* QP = qperm + (size_t)f * qout_stride;
+  const uint32_t* KI = qkidx + (size_t)f * qout_stride;
+  const uint32_t* TW = twscr + (size_t)f * tw_stride;
 #if OB_HPASS == 1
   uint32_t(*P)[KP_PSTRIDE] = reinterpret_cast<uint32_t(*)[KP_PSTRIDE]>(patchbuf + KP_PGUARD_LO + wave * (KP_ROWS * KP_PSTRIDE));
   // B operand of the horizontal pass (lane = output column c of a 16-column
@@ -2151,9 +2203,33 @@ __device__ __forceinline__ void ob_body(OB_KERNEL_ARGS, const uint8_t* __restric
     const int e = __builtin_amdgcn_readlane(excl, l);  // l is uniform
     // position o of the processing order (qperm, k_quadtree) -> winner i of
     // level l, written at output position e + i
-    const int i = (int)__builtin_amdgcn_readfirstlane(QP[A.kout_off[l] + (o - e)]);
-    const uint32_t key = __builtin_amdgcn_readfirstlane(Q[A.kout_off[l] + i]);
+    const int r = A.kout_off[l] + (o - e);
+    const int i = (int)__builtin_amdgcn_readfirstlane(QP[r]);
     BriefKp k;
+    k.oi2 = -1;
+    k.skip = false;
+    // twin rows (LevelInfo::twin): the winner's key index, looked up in the
+    // bitmap of the pair's other level t.  Set there, the same key won in
+    // both levels: the alias level's keypoint is skipped (scalar work only,
+    // no patch load), the unique level's also writes that row -- winner
+    // QP[t][rank of the key index in t's bitmap]
+    const int t = A.twin[l];
+    if (TWINS && t >= 0 && ((tvmask >> l) & (tvmask >> t) & 1u)) {
+      const uint32_t kk = __builtin_amdgcn_readfirstlane(KI[r]);
+      // {bitmap word, winners below it} of the key index, one 8-byte load
+      const uint2 wp = reinterpret_cast<const uint2*>(TW + A.tw_off[t])[kk >> 5];
+      const uint32_t w = __builtin_amdgcn_readfirstlane(wp.x), pc = __builtin_amdgcn_readfirstlane(wp.y);
+      const uint32_t bit = 1u << (kk & 31);
+      if (w & bit) {
+        if (A.unique[l] != l) {
+          k.skip = true;
+          return k;
+        }
+        const int ia = (int)__builtin_amdgcn_readfirstlane(QP[A.kout_off[t] + (int)pc + __popc(w & (bit - 1u))]);
+        k.oi2 = __builtin_amdgcn_readlane(excl, t) + ia;
+      }
+    }
+    const uint32_t key = __builtin_amdgcn_readfirstlane(Q[A.kout_off[l] + i]);
     k.oi = e + i;
     k.l = l;
     k.x = orbx_key_x(key, A.key_xs) + ORBX_MINB;
@@ -2191,11 +2267,21 @@ __device__ __forceinline__ void ob_body(OB_KERNEL_ARGS, const uint8_t* __restric
   int o = g;
   const int oend = total;
 #endif
+  // the next position from p on that is computed (an alias level's twin
+  // rows are passed over); oend when there is none
+  BriefKp cur;
+  auto advance = [&](int p) {
+    for (; p < oend; p += stride) {
+      cur = locate(p);
+      if (!cur.skip) break;
+    }
+    return p;
+  };
+  o = advance(o);
   if (o >= oend) return;
-  BriefKp cur = locate(o);
   BriefRegs<LB> R;
   brief_issue(cur, R, lane);
-  for (; o < oend; o += stride) {  // wave-uniform
+  for (int onext; o < oend; o = onext) {  // wave-uniform
   // ---- stage this keypoint's patch (unblurred level), reflect-101 outside ----
   [[maybe_unused]] uint32_t hte = 0;  // OB_HPASS 0: the keypoint's task bytes
   if constexpr (LB) {
@@ -2209,10 +2295,8 @@ __device__ __forceinline__ void ob_body(OB_KERNEL_ARGS, const uint8_t* __restric
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   const BriefKp me = cur;
-  if (o + stride < oend) {  // next keypoint: its patch loads stay in flight
-    cur = locate(o + stride);
-    brief_issue(cur, R, lane);
-  }
+  onext = advance(o + stride);
+  if (onext < oend) brief_issue(cur, R, lane);  // next keypoint: its patch loads stay in flight
   const int l = me.l, x = me.x, score = me.score, px0 = me.px0;
   // BRIEF (:57-73) on GaussianBlur(7x7, sigma 2): separable and exact,
   // out = (sum_j k_j H(r+j-3) + 32768) >> 16 with H = sum_i k_i p(c+i-3)
@@ -2451,6 +2535,8 @@ __device__ __forceinline__ void ob_body(OB_KERNEL_ARGS, const uint8_t* __restric
   if (lane < 4) {
     const uint64_t w = lane == 0 ? words[0] : lane == 1 ? words[1] : lane == 2 ? words[2] : words[3];
     reinterpret_cast<uint64_t*>(descf + (uint32_t)me.oi * 32u)[lane] = w;
+    // the twin row in the alias level: the same bytes (wave-uniform branch)
+    if (me.oi2 >= 0) reinterpret_cast<uint64_t*>(descf + (uint32_t)me.oi2 * 32u)[lane] = w;
   }
 #ifdef OB_PROBE_NOSTORE
   if (dbg == 0x5EED)
@@ -2469,16 +2555,31 @@ __device__ __forceinline__ void ob_body(OB_KERNEL_ARGS, const uint8_t* __restric
     kp.octave = l;
     kp.class_id = -1;
     *reinterpret_cast<orbx_keypoint*>(reinterpret_cast<uint8_t*>(kpsf) + (uint32_t)me.oi * (uint32_t)sizeof(orbx_keypoint)) = kp;
+    if (me.oi2 >= 0) {  // the twin row: octave, scale and size of the alias level (>= 1)
+      const int l2 = A.twin[l];
+      kp.x = (float)x * A.scale[l2];
+      kp.y = (float)me.y * A.scale[l2];
+      kp.size = (float)A.patch[l2];
+      kp.octave = l2;
+      *reinterpret_cast<orbx_keypoint*>(reinterpret_cast<uint8_t*>(kpsf) + (uint32_t)me.oi2 * (uint32_t)sizeof(orbx_keypoint)) = kp;
+    }
   }
   }
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OB_WPE))) void k_orient_brief(OB_KERNEL_ARGS) {
-  ob_body<false>(OB_KERNEL_PASS, nullptr, 0);
+  ob_body<false, false>(OB_KERNEL_PASS, nullptr, 0);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OB_WPE))) void k_orient_brief_tw(OB_KERNEL_ARGS) {
+  ob_body<false, true>(OB_KERNEL_PASS, nullptr, 0);
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OB_WPE))) void k_orient_brief_lb(
     OB_KERNEL_ARGS, const uint8_t* __restrict__ blur, size_t bstride) {
-  ob_body<true>(OB_KERNEL_PASS, blur, bstride);
+  ob_body<true, false>(OB_KERNEL_PASS, blur, bstride);
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OB_WPE))) void k_orient_brief_lb_tw(
+    OB_KERNEL_ARGS, const uint8_t* __restrict__ blur, size_t bstride) {
+  ob_body<true, true>(OB_KERNEL_PASS, blur, bstride);
 }
 
 // ---------------------------------------------------------------------------

@@ -9,6 +9,9 @@
  *   qkeys/qnode        = DistributeOctTree scratch (per level)
  *   qout [kcap] u32    = per-level selected keys, packed like slots
  *   lcount[nlevels]    = per-level selected counts
+ *   twvalid[nlevels]   = per level: its twin data below is there (LevelInfo::twin)
+ *   qkidx [kcap] u32   = the winners' key indices, in qperm's order
+ *   twscr [tw_words]   = the twin pairs' winner bitmaps and rank prefixes
  * "unique" levels: level l shares level l-1's pixels when their sizes are
  * equal (cv::resize copies when dsize == ssize); with the reference's
  * std::partial_sum scale table this is always true for l == 1.
@@ -52,6 +55,13 @@ struct LevelInfo {
   int blur_tiles_x;
   int wcell;
   int key_xs;          /* FAST key packing shift (orbx_pack_key)                 */
+  /* twin rows: a unique level and its first alias level run the quadtree over
+   * the same key list, so a key index that wins in both gives two output rows
+   * that differ in octave / scale only; k_orient_brief computes the unique
+   * level's and writes both.  twin = the other level of the pair (-1: none);
+   * tw_off = this level's block of the per-frame twin scratch, in words:
+   * tw_nw pairs {bitmap word, winners below it} over the key indices */
+  int twin, tw_off, tw_nw, tw_pad;
 };
 
 #define ORBX_BLUR_TW 128
@@ -178,6 +188,10 @@ struct BriefArgs {
   int patch[ORBX_MAX_LEVELS];
   uint32_t umaxw[4]; /* IC_Angle umax[0..15], one byte each */
   int key_xs;        /* orbx_pack_key shift */
+  /* twin rows (LevelInfo::twin), per launch: the other level of this level's
+   * pair (-1: none, or the plan option is off) and the pairs' blocks of the
+   * twin scratch */
+  int twin[ORBX_MAX_LEVELS], tw_off[ORBX_MAX_LEVELS];
 };
 
 /* fused pyramid segment: destination levels lev[1..nl] computed in one

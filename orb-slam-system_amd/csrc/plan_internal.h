@@ -37,8 +37,15 @@ struct orbx_plan {
   orbx::DevBuf<int16_t> d_alpha, d_beta;
   orbx::DevBuf<uint8_t> d_pyr, d_blur;
   orbx::DevBuf<uint32_t> d_slots, d_ccount, d_qkeys, d_qout;
-  orbx::DevBuf<uint32_t> d_qperm; /* per level: k_orient_brief's processing order (k_quadtree) */
+  orbx::DevBuf<uint32_t> d_qperm; /* per level: k_orient_brief's processing order (k_quadtree); then the twin tables below */
   orbx::DevBuf<int32_t> d_qnode;
+  /* twin rows (LevelInfo::twin; plans with an alias level), parts of d_qperm's
+   * allocation, not owned: the winners' key indices (qperm's layout), the
+   * pairs' winner bitmaps with their rank prefixes, and per level whether its
+   * bitmap is there */
+  uint32_t *d_qkidx = nullptr, *d_twscr = nullptr;
+  int* d_twvalid = nullptr;
+  size_t tw_stride = 0;
   orbx::DevBuf<int> d_lcount, d_err;
   orbx::DevBuf<int> d_fs_cnt; /* k_fast_strips' striped debug counters (FS_CNT_LINES x FS_CNT_STRIDE) */
   long long fs_dense_total = 0, fs_ovf_total = 0; /* their sums since each was last read */

@@ -48,6 +48,7 @@ OK, ERR_ARG, ERR_CELL_ROI, ERR_LEVEL_SIZE, ERR_QUADTREE, ERR_CAPACITY, ERR_UNSUP
 ORBV_QUERY_GATED = 1  # orbv_db_query_batch flags (include/orbx.h)
 ORBM_PLAN_ZERO_TAIL, ORBM_PLAN_VALU = 1, 2  # orbm_plan_set_options flags (include/orbx.h)
 ORBX_PLAN_PYR_TILES, ORBX_PLAN_BRIEF_PATCH, ORBX_PLAN_BRIEF_LEVEL, ORBX_PLAN_FAST_DENSE = 1, 8, 16, 64  # orbx_plan_set_options flags
+ORBX_PLAN_NO_TWINS = 128
 
 EXPORTED = [
     "orbx_abi_version", "orbx_status_string", "orbx_device_count", "orbx_tables",
@@ -1498,17 +1499,20 @@ class Plan:
         _check(_lib.orbx_plan_fast_dense_strips(self._h, ctypes.byref(d)), "orbx_plan_fast_dense_strips")
         return {"fast_overflow_strips": v.value, "fast_dense_strips": d.value}
 
-    def set_options(self, pyramid="auto", brief="auto", fast_post="auto"):
+    def set_options(self, pyramid="auto", brief="auto", fast_post="auto", twins="auto"):
         """pyramid: 'auto' or 'tiles' (k_pyramid, the one pyramid path since
         the round-4 streaming kernels were retired); brief: 'auto' (the
         planner's choice), 'patch' (per-keypoint blur, k_orient_brief) or
         'level' (every level blurred once, k_blur + k_orient_brief_lb).
         fast_post: 'auto' (FAST's post-pass chosen per strip by its corner
         count) or 'dense' (every strip takes the four-wave row-mask form).
-        Every combination gives the same results."""
+        twins: 'auto' (a keypoint kept both in a level and in a level aliasing
+        it is computed once and written to both rows) or 'off' (computed once
+        per level).  Every combination gives the same results."""
         flags = {"auto": 0, "tiles": ORBX_PLAN_PYR_TILES}[pyramid]
         flags |= {"auto": 0, "patch": ORBX_PLAN_BRIEF_PATCH, "level": ORBX_PLAN_BRIEF_LEVEL}[brief]
         flags |= {"auto": 0, "dense": ORBX_PLAN_FAST_DENSE}[fast_post]
+        flags |= {"auto": 0, "off": ORBX_PLAN_NO_TWINS}[twins]
         _check(_lib.orbx_plan_set_options(self._h, flags), "orbx_plan_set_options")
 
     def level(self, frame, lvl, stream=None):
