@@ -497,10 +497,28 @@ int orbm_plan_stage_times(orbm_plan* mp, double* ms, int* launches, int nstages)
  *                      reference's 728-entry BRIEF pattern leaves them 0) --
  *                      so the distance kernels skip those two dwords;
  * ORBM_PLAN_VALU       distances by xor/popcount on the VALU instead of the
- *                      i8 MFMA formulation (same results; for testing). */
+ *                      i8 MFMA formulation (same results; for testing);
+ * ORBM_PLAN_NO_FOLD    every selected keypoint gets a distance row and column
+ *                      of its own.  By default selected keypoints of a frame
+ *                      with byte-identical descriptors (a keypoint kept in
+ *                      level 0 and in its alias level 1) are computed once, in
+ *                      pairs, and both get the result: the same matches, about
+ *                      half the distance work on extractor outputs.  Lists
+ *                      beyond 8192 keypoints (16384 with ORBM_PLAN_ZERO_TAIL)
+ *                      and ORBM_PLAN_VALU run unfolded.
+ * If side B is side A one frame back (d_kps_b + kcap == d_kps_a,
+ * d_desc_b + kcap*32 == d_desc_a, d_count_b + 1 == d_count_a: a frame against
+ * its predecessor out of one buffer of npairs + 1 frames), every frame is
+ * selected once; the result is the same. */
 #define ORBM_PLAN_ZERO_TAIL 1
 #define ORBM_PLAN_VALU 2
+#define ORBM_PLAN_NO_FOLD 4
 int orbm_plan_set_options(orbm_plan* mp, int flags);
+/* Folding counters of the plan's last orbm_plan_match_frames call, summed over
+ * its pairs (waits for the device): out[0] selected keypoints of the
+ * A sides, out[1] those among them computed as another's copy (followers),
+ * out[2] / out[3] the same for the B sides.  0 followers when unfolded. */
+int orbm_plan_fold_stats(orbm_plan* mp, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------
  * Stereo matcher: Frame::ComputeStereoMatches (src/Frame.cc:446-620), the

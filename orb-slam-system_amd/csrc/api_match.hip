@@ -9,6 +9,7 @@
 
 #include "../../include/orbx.h"
 #include "call_arena.h"
+#include "match_fold_hash.h"
 #include "match_internal.h"
 
 namespace orbx {
@@ -19,11 +20,12 @@ __global__ void k_match_cand_rows(const MProblem*, const MNodePair*, const uint4
                                   uint2*, int4*, int2*);
 __global__ void k_match_gather2(const MProblem*, const MNodePair*, uint4*, uint32_t*);
 typedef int v4i_ __attribute__((ext_vector_type(4)));
-template <int NK>
-__global__ void k_match_expand2(const MProblem*, const MNodePair*, v4i_*);
-template <int NK, int RT, bool PK, int CS>
+template <int NK, bool FOLD>
+__global__ void k_match_expand2(const MProblem*, const MNodePair*, v4i_*, const MFoldPair*,
+                                const uint32_t*);
+template <int NK, int RT, bool PK, int CS, bool FOLD>
 __global__ void k_match_cand_mfma(const MProblem*, const MNodePair*, const v4i_*, uint2*, int4*,
-                                  int2*);
+                                  int2*, const MFoldPair*, const uint32_t*);
 
 __global__ void k_match_resolve(const MProblem*, const MNodePair*, int, int, const uint2*,
                                 const int4*, int2*);
@@ -31,11 +33,12 @@ __global__ void k_match_resolve_spec(const MProblem*, const MNodePair*, int, con
                                      const int4*, int2*, int);
 __global__ void k_match_finalize(const MProblem*, const MNodePair*, const int4*, int2*, int*,
                                  const int*);
-__global__ void k_match_setup(MProblem*, MNodePair*, int, const orbx_keypoint*, const uint8_t*,
-                              const orbx_keypoint*, const uint8_t*, int, int, const uint32_t*, int32_t*,
-                              int*, float, int, int*);
-__global__ void k_match_select(MProblem*, MNodePair*, const orbx_keypoint*, const int*,
-                               const orbx_keypoint*, const int*, int, int, uint32_t*);
+__global__ void k_match_setup(MProblem*, MNodePair*, MFoldPair*, int, const orbx_keypoint*,
+                              const uint8_t*, const orbx_keypoint*, const uint8_t*, int, int, int,
+                              const uint32_t*, int32_t*, int*, float, int, int*);
+__global__ void k_match_select(MProblem*, MNodePair*, MFoldPair*, const orbx_keypoint*, const uint8_t*,
+                               const int*, const orbx_keypoint*, const uint8_t*, const int*, int, int,
+                               int, int, uint32_t*, uint32_t*, uint32_t*);
 __global__ void k_hamming_pairs(const uint8_t*, const uint8_t*, const int32_t*, const int32_t*,
                                 int, int32_t*);
 }  // namespace orbx
@@ -76,6 +79,9 @@ struct MatchScratch {
   int2* ev = nullptr;        // rows
   int* last = nullptr;       // per KF1 feature
   int* last_off = nullptr;   // per problem: its offset in last
+  // folded lists (batched plan; MFoldPair), or nullptr: whole lists
+  const MFoldPair* fps = nullptr;
+  const uint32_t* fmap = nullptr;
 };
 
 // one launch's extent
@@ -111,30 +117,36 @@ void launch_match(const MProblem* d_probs, const MNodePair* d_nps, const MatchSh
         const bool csplit = (size_t)sh.nnp * (size_t)((sh.max_n1 + 128 * MC_RT - 1) / (128 * MC_RT)) < (size_t)MC_CSPLIT_WGS &&
                             sh.max_n2 >= 256;
         const dim3 g1((sh.max_n1 + 128 * MC_RT - 1) / (128 * MC_RT), sh.nnp), g4((sh.max_n1 + 31) / 32, sh.nnp);
-#define MC_LAUNCH(NK, PK)                                                                               \
+#define MC_LAUNCH(NK, PK, FOLD)                                                                         \
   do {                                                                                                  \
+    hipLaunchKernelGGL((k_match_expand2<NK, FOLD>),                                                     \
+                       dim3((sh.max_n2 * ORBM_EXPAND_PER_POS(NK) + 255) / 256, sh.nnp), dim3(256), 0, s, \
+                       d_probs, d_nps, gx2, sc.fps, sc.fmap);                                           \
     if (csplit)                                                                                         \
-      hipLaunchKernelGGL((k_match_cand_mfma<NK, 1, PK, 4>), g4, dim3(256), 0, s, d_probs, d_nps, gx2,   \
-                         sc.cand, sc.rowinfo, sc.ev);                                                \
+      hipLaunchKernelGGL((k_match_cand_mfma<NK, 1, PK, 4, FOLD>), g4, dim3(256), 0, s, d_probs, d_nps,  \
+                         gx2, sc.cand, sc.rowinfo, sc.ev, sc.fps, sc.fmap);                             \
     else                                                                                                \
-      hipLaunchKernelGGL((k_match_cand_mfma<NK, MC_RT, PK, 1>), g1, dim3(256), 0, s, d_probs, d_nps,    \
-                         gx2, sc.cand, sc.rowinfo, sc.ev);                                           \
+      hipLaunchKernelGGL((k_match_cand_mfma<NK, MC_RT, PK, 1, FOLD>), g1, dim3(256), 0, s, d_probs,     \
+                         d_nps, gx2, sc.cand, sc.rowinfo, sc.ev, sc.fps, sc.fmap);                      \
   } while (0)
+        // positions in the accumulator while they fit its 2^MC_PB(NK) slots;
+        // folded lists (the batched plan, match_fold_ok) in that form only
+        const bool pk = ORBM_FP4 && MC_PK && sh.max_n2 <= (sh.six_words ? 1 << 14 : 1 << 13);
+        const bool fold = pk && sc.fps && sc.fmap;
         if (sh.six_words) {
-          hipLaunchKernelGGL(k_match_expand2<6>, dim3((sh.max_n2 * ORBM_EXPAND_PER_POS(6) + 255) / 256, sh.nnp), dim3(256), 0, s,
-                             d_probs, d_nps, gx2);
-          // positions in the accumulator while they fit its 2^MC_PB(6) slots
-          if (ORBM_FP4 && MC_PK && sh.max_n2 <= (1 << 14))
-            MC_LAUNCH(6, ORBM_FP4 != 0);
+          if (fold)
+            MC_LAUNCH(6, ORBM_FP4 != 0, ORBM_FP4 != 0);
+          else if (pk)
+            MC_LAUNCH(6, ORBM_FP4 != 0, false);
           else
-            MC_LAUNCH(6, false);
+            MC_LAUNCH(6, false, false);
         } else {
-          hipLaunchKernelGGL(k_match_expand2<8>, dim3((sh.max_n2 * ORBM_EXPAND_PER_POS(8) + 255) / 256, sh.nnp), dim3(256), 0, s,
-                             d_probs, d_nps, gx2);
-          if (ORBM_FP4 && MC_PK && sh.max_n2 <= (1 << 13))
-            MC_LAUNCH(8, ORBM_FP4 != 0);
+          if (fold)
+            MC_LAUNCH(8, ORBM_FP4 != 0, ORBM_FP4 != 0);
+          else if (pk)
+            MC_LAUNCH(8, ORBM_FP4 != 0, false);
           else
-            MC_LAUNCH(8, false);
+            MC_LAUNCH(8, false, false);
         }
 #undef MC_LAUNCH
       } else {
@@ -397,9 +409,18 @@ struct orbm_plan {
    * default: any other descriptor source gets all 8 dwords. */
   bool six_words = false;
   bool force_valu = false; /* ORBM_PLAN_VALU: popcount kernel instead of the MFMA path */
+  bool no_fold = false;    /* ORBM_PLAN_NO_FOLD: whole lists (the kernels' FOLD = false forms) */
+  int last_npairs = 0;     /* orbm_plan_fold_stats: the last call's pairs */
   DevBuf<MProblem> d_probs;
   DevBuf<MNodePair> d_nps;
+  /* per list (2 per pair) topn dwords each: the selection, then MFoldPair's
+   * tables (fmap), then k_match_select's entry states (fst); the pairs'
+   * MFoldPair records behind them -- one allocation */
   DevBuf<uint32_t> d_sel;
+  size_t lists() const { return (size_t)max_pairs * 2 * topn; }
+  uint32_t* d_fmap() const { return (uint32_t*)d_sel + lists(); }
+  uint32_t* d_fst() const { return (uint32_t*)d_sel + 2 * lists(); }
+  MFoldPair* d_fps() const { return reinterpret_cast<MFoldPair*>((uint32_t*)d_sel + 3 * lists()); }
   /* launch_match's scratch (MatchScratch) */
   DevBuf<uint4> d_gdesc2;
   DevBuf<uint8_t> d_gx2;
@@ -413,7 +434,18 @@ struct orbm_plan {
   /* no validity masks (gval2); the +-1 bytes unless the popcount path is forced */
   MatchScratch scratch() const {
     uint8_t* const gx2 = force_valu ? nullptr : d_gx2;
-    return MatchScratch{d_gdesc2, nullptr, gx2, d_cand, d_rowinfo, d_ev, d_last, d_last_off};
+    const bool f = fold();
+    return MatchScratch{d_gdesc2, nullptr, gx2, d_cand, d_rowinfo, d_ev, d_last, d_last_off,
+                        f ? (const MFoldPair*)d_fps() : nullptr, f ? (const uint32_t*)d_fmap() : nullptr};
+  }
+
+  /* identical descriptors of a list folded: the MFMA path with positions in
+   * the accumulator unless ORBM_PLAN_NO_FOLD -- launch_match's own conditions
+   * for that path (at most 65535 node pairs, gx2, no validity arrays, list
+   * length), so the tables are built exactly when the FOLD kernels run */
+  bool fold() const {
+    return !no_fold && !force_valu && ORBM_MFMA && ORBM_FP4 && MC_PK && max_pairs <= 65535 &&
+           topn <= (six_words ? 1 << 14 : 1 << 13);
   }
 };
 
@@ -429,7 +461,8 @@ extern "C" int orbm_plan_create(int max_pairs, int kcap, int topn, int device, o
   m->kcap = kcap;
   m->topn = topn;
   const size_t P = (size_t)max_pairs, rows = P * topn;
-  if (m->d_probs.alloc(P) || m->d_nps.alloc(P) || m->d_sel.alloc(P * 2 * topn) ||
+  if (m->d_probs.alloc(P) || m->d_nps.alloc(P) ||
+      m->d_sel.alloc(3 * P * 2 * topn + P * sizeof(MFoldPair) / sizeof(uint32_t)) ||
       m->d_cand.alloc(rows * ORBM_T) || m->d_gdesc2.alloc(rows * 2) || m->d_gx2.alloc(rows * 256) ||
       m->d_rowinfo.alloc(rows) || m->d_ev.alloc(rows) || m->d_last.alloc(P * kcap) ||
       m->d_last_off.alloc(P))
@@ -444,9 +477,30 @@ extern "C" int orbm_plan_destroy(orbm_plan* m) {
 }
 
 extern "C" int orbm_plan_set_options(orbm_plan* m, int flags) {
-  if (!m || (flags & ~(ORBM_PLAN_ZERO_TAIL | ORBM_PLAN_VALU))) return ORBX_ERR_ARG;
+  if (!m || (flags & ~(ORBM_PLAN_ZERO_TAIL | ORBM_PLAN_VALU | ORBM_PLAN_NO_FOLD))) return ORBX_ERR_ARG;
   m->six_words = (flags & ORBM_PLAN_ZERO_TAIL) != 0;
   m->force_valu = (flags & ORBM_PLAN_VALU) != 0;
+  m->no_fold = (flags & ORBM_PLAN_NO_FOLD) != 0;
+  return ORBX_OK;
+}
+
+extern "C" int orbm_plan_fold_stats(orbm_plan* m, int64_t* out) {
+  if (!m || !out) return ORBX_ERR_ARG;
+  ORBX_TRY(hipSetDevice(m->device));
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (m->last_npairs < 1) return ORBX_OK;
+  // the per-pair counts k_match_select left; summed here, no device counter
+  std::vector<MNodePair> nps(m->last_npairs);
+  std::vector<MFoldPair> fps(m->last_npairs);
+  ORBX_TRY(hipDeviceSynchronize());  // that call's stream may be gone by now
+  ORBX_TRY(hipMemcpy(nps.data(), m->d_nps, nps.size() * sizeof(MNodePair), hipMemcpyDeviceToHost));
+  ORBX_TRY(hipMemcpy(fps.data(), m->d_fps(), fps.size() * sizeof(MFoldPair), hipMemcpyDeviceToHost));
+  for (int p = 0; p < m->last_npairs; ++p) {
+    out[0] += nps[p].n1;
+    out[1] += nps[p].n1 - fps[p].n1u;
+    out[2] += nps[p].n2;
+    out[3] += nps[p].n2 - fps[p].n2u;
+  }
   return ORBX_OK;
 }
 
@@ -474,11 +528,19 @@ extern "C" int orbm_plan_match_frames(orbm_plan* m, int npairs, const orbx_keypo
   ORBX_TRY(hipSetDevice(m->device));
   hipStream_t s = (hipStream_t)stream;
   m->timer.begin(ORBX_STAGE_MSELECT, s);
+  // side B = side A one frame back (a tracker's frame against its
+  // predecessor, out of one buffer): npairs + 1 frames, each selected once
+  const int shifted = kps_a == kps_b + m->kcap && desc_a == desc_b + (size_t)m->kcap * 32 &&
+                      count_a == count_b + 1;
+  const int hbits = m->fold() ? orbm_fold_hbits(m->topn) : 0;
+  const size_t fold_lds = hbits ? sizeof(uint32_t) << hbits : 0;
   hipLaunchKernelGGL(k_match_setup, dim3((npairs + 63) / 64), dim3(64), 0, s, m->d_probs,
-                     m->d_nps, npairs, kps_a, desc_a, kps_b, desc_b, m->kcap, m->topn, m->d_sel,
-                     match12, nmatches, nnratio, check_ori ? 1 : 0, m->d_last_off);
-  hipLaunchKernelGGL(k_match_select, dim3(npairs, 2), dim3(256), 0, s, m->d_probs, m->d_nps,
-                     kps_a, count_a, kps_b, count_b, m->kcap, m->topn, m->d_sel);
+                     m->d_nps, m->d_fps(), npairs, kps_a, desc_a, kps_b, desc_b, m->kcap, m->topn,
+                     shifted, m->d_sel, match12, nmatches, nnratio, check_ori ? 1 : 0, m->d_last_off);
+  hipLaunchKernelGGL(k_match_select, shifted ? dim3(npairs + 1) : dim3(npairs, 2), dim3(256), fold_lds,
+                     s, m->d_probs, m->d_nps, m->d_fps(), kps_a, desc_a, count_a, kps_b, desc_b, count_b,
+                     m->kcap, m->topn, shifted, hbits, m->d_sel, m->d_fmap(), m->d_fst());
+  m->last_npairs = npairs;
   m->timer.end(ORBX_STAGE_MSELECT, s);
   const MatchShape sh = {npairs, npairs, npairs * m->topn, 0, m->topn, m->topn, m->kcap, m->six_words};
   launch_match(m->d_probs, m->d_nps, sh, m->scratch(), s, &m->timer);

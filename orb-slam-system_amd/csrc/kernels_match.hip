@@ -10,7 +10,8 @@
 // unless another launcher is named:
 //   k_match_setup         batched plan only (orbm_plan_match_frames), before
 //   k_match_select        launch_match: the problem and node-pair tables,
-//                         then the top-n keypoints of each frame
+//                         then the top-n keypoints of each frame and the
+//                         list's fold table (identical descriptors once)
 //   k_match_expand2       candidates on the matrix cores (at most 65535 node
 //   k_match_cand_mfma     pairs, no validity arrays, ORBM_MFMA): list2 as
 //                         +-1 operands, then distances by MFMA
@@ -31,6 +32,7 @@
 #include <type_traits>
 
 #include "../../include/orbx.h"
+#include "match_fold_hash.h"
 #include "match_internal.h"
 #include "orbm_device.h"
 #include "wave_ops.h"
@@ -476,17 +478,28 @@ __device__ __forceinline__ v4i_ pm1_nibs(uint32_t lo16, uint32_t hi16, bool pos)
 // gx2[(g2 + j) * NK + 2 * m + h] = bits 16h .. 16h+15 of dwords 2m and
 // 2m + 1 as +-1 nibbles (16 B per lane half and K step).  The list2 gather
 // and the expansion in one pass (the MFMA path needs no packed copy).
-template <int NK>
+// FOLD (batched plan): list2's representatives only, in folded order
+// (MFoldPair): gx2[g2 + u] is the u-th representative.
+template <int NK, bool FOLD>
 __global__ __launch_bounds__(256) void k_match_expand2(const MProblem* __restrict__ probs,
                                                        const MNodePair* __restrict__ nps,
-                                                       v4i_* __restrict__ gx2) {
+                                                       v4i_* __restrict__ gx2,
+                                                       const MFoldPair* __restrict__ fps,
+                                                       const uint32_t* __restrict__ fmap) {
   const MNodePair NP = nps[blockIdx.y];
   constexpr int PER = ORBM_EXPAND_PER_POS(NK);
   const int i = blockIdx.x * 256 + threadIdx.x;  // (position, K step)
   const int j = i / PER, s = i - j * PER;
-  if (j >= NP.n2) return;
+  int pos = j;
+  if constexpr (FOLD) {
+    const MFoldPair FP = fps[blockIdx.y];
+    if (j >= FP.n2u) return;
+    pos = (int)(fmap[FP.f2 + j] & 0xFFFFu);
+  } else {
+    if (j >= NP.n2) return;
+  }
   const MProblem& P = probs[NP.prob];
-  const uint32_t idx2 = P.feat2[NP.off2 + j];
+  const uint32_t idx2 = P.feat2[NP.off2 + pos];
   v4i_* o = gx2 + ((size_t)(NP.g2 + j) * PER + s) * 2;
 #if ORBM_FP4
   const uint2 w = reinterpret_cast<const uint2*>(P.desc2 + (size_t)idx2 * 32)[s];
@@ -498,8 +511,13 @@ __global__ __launch_bounds__(256) void k_match_expand2(const MProblem* __restric
   o[1] = pm1_bytes(w >> 16, true);
 #endif
 }
-template __global__ void k_match_expand2<6>(const MProblem*, const MNodePair*, v4i_*);
-template __global__ void k_match_expand2<8>(const MProblem*, const MNodePair*, v4i_*);
+#define ME_INST(NK, FOLD) \
+  template __global__ void k_match_expand2<NK, FOLD>(const MProblem*, const MNodePair*, v4i_*, const MFoldPair*, const uint32_t*);
+ME_INST(6, false)
+ME_INST(8, false)
+ME_INST(6, true)
+ME_INST(8, true)
+#undef ME_INST
 
 // one 32-position x 32-row tile: distances on the MFMA, keys and top-T
 // insertions of the lane's 16 (row, position) values on the VALU
@@ -691,13 +709,25 @@ __device__ __forceinline__ void mfma_tile_pk(const v4i_ (&af)[NS], const v4i_ (&
 // the list's tiles CS ways; their top-T lists merge through LDS at the end
 // (the exact top-T of the union: each part's top-T holds the union's members
 // from that part).
-template <int NK, int RT, bool PK, int CS>
+// FOLD (batched plan, PK form): rows are list1's representatives and
+// positions list2's (MFoldPair; gx2 from k_match_expand2's FOLD form), so a
+// key's position is a folded rank until the row's list is written out.
+// There every key goes back to its representative's position and brings its
+// follower's key (same distance) along, the ORBM_T smallest of the up to 16
+// stay, and the record goes to the representative's row and, with its own
+// idx1, to the follower's.  Exact: representatives keep their positions'
+// order, so a representative u' ahead of u in folded order has
+// (h', first(u')) < (h, first(u)) <= any key of u; if u has a key among the
+// whole list's ORBM_T smallest, fewer than ORBM_T representatives are ahead of
+// it, so u is among the folded list's ORBM_T smallest.
+template <int NK, int RT, bool PK, int CS, bool FOLD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_WPE))) void k_match_cand_mfma(
     const MProblem* __restrict__ probs, const MNodePair* __restrict__ nps,
     const v4i_* __restrict__ gx2, uint2* __restrict__ cand, int4* __restrict__ rowinfo,
-    int2* __restrict__ ev) {
+    int2* __restrict__ ev, const MFoldPair* __restrict__ fps, const uint32_t* __restrict__ fmap) {
   static_assert(NK == 6 || NK == 8, "6 or 8 live descriptor dwords");
   static_assert(CS == 1 || (CS == 4 && RT == 1), "column split: 4 waves on one row tile");
+  static_assert(!FOLD || PK, "folded lists: positions in the accumulator only");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h = lane >> 5, c = lane & 31;
@@ -705,12 +735,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
   frame_unit(bx, np);  // a node pair's row chunks share one L2 (its list2)
   const MNodePair NP = nps[np];
   const int a0 = bx * (CS == 1 ? 128 * RT : 32);
-  if (a0 >= NP.n1) return;  // workgroup-uniform
+  MFoldPair FP = {NP.n1, NP.n2, 0, 0};
+  if constexpr (FOLD) FP = fps[np];
+  const int n1 = FP.n1u;  // rows and positions of this launch: representatives when FOLD
+  if (a0 >= n1) return;  // workgroup-uniform
+  // a wave past the list's rows has no record to write (whole lists: left in
+  // the workgroup, the parent's form)
+  if (FOLD && CS == 1 && a0 + 32 * RT * wave >= n1) return;
   const MProblem P = probs[NP.prob];
   const uint32_t* f2 = P.feat2 + NP.off2;
-  const int n2 = NP.n2;
+  const int n2 = FP.n2u;
   constexpr int NS = ORBM_EXPAND_PER_POS(NK);  // MFMA K steps per tile
   int a[RT], idx1[RT];
+  int fol1[RT];  // FOLD: the row's follower position in list1, or ORBM_NO_FOLLOWER
   bool act[RT], v1[RT];
   v4i_ bf[RT][NS];
   uint32_t L[RT][ORBM_T];
@@ -724,11 +761,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
     a[t] = a0 + 32 * (RT * (CS == 1 ? wave : 0) + t) + c;
-    act[t] = a[t] < NP.n1;
+    act[t] = a[t] < n1;
     idx1[t] = 0;
     v1[t] = false;
+    fol1[t] = (int)ORBM_NO_FOLLOWER;
     uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
     if (act[t]) {
+      if constexpr (FOLD) {  // the representative's own position, from here on
+        const uint32_t m = fmap[FP.f1 + a[t]];
+        a[t] = (int)(m & 0xFFFFu);
+        fol1[t] = (int)(m >> 16);
+      }
       idx1[t] = (int)P.feat1[NP.off1 + a[t]];
       v1[t] = !(P.valid1 && !P.valid1[idx1[t]]);
       q0 = reinterpret_cast<const uint4*>(P.desc1 + (size_t)idx1[t] * 32)[0];
@@ -845,7 +888,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
         if (__ballot(kk < Lt[ORBM_T - 1])) topk_insert(Lt, kk);
       }
     }
-    const bool full = Lt[ORBM_T - 1] < sent;
+    bool full = Lt[ORBM_T - 1] < sent;
 #pragma unroll
     for (int u = 0; u < ORBM_T; ++u) {
 #if ORBM_FP4
@@ -854,36 +897,72 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MC_WPE))) v
 #endif
       if (Lt[u] >= (PK ? (uint32_t)P.dcap << 16 : sent)) Lt[u] = 0xFFFFFFFFu;
     }
-    if (!act[t]) continue;
-    const int r = NP.row_base + a[t];
-    ev[r] = make_int2(-1, 0);
-    if (!v1[t]) {
-      rowinfo[r] = make_int4(0, 0, 0, idx1[t]);
-      continue;
-    }
-    const int minD = Lt[0] != 0xFFFFFFFFu ? (int)(Lt[0] >> 16) : (1 << 20);
-    rowinfo[r] = make_int4(1, full ? ORBM_T + 1 : 0, minD, idx1[t]);
-    if (minD >= P.th_low) continue;
-    uint4* out = reinterpret_cast<uint4*>(cand + (size_t)r * ORBM_T);
+    if constexpr (FOLD) {
+      // folded ranks back to list positions (still ascending: a rank orders
+      // like its representative's position), then the followers' keys
+      uint32_t fk[ORBM_T];
 #pragma unroll
-    for (int u = 0; u < ORBM_T / 2; ++u) {
-      const uint32_t ka = Lt[2 * u], kb = Lt[2 * u + 1];
-      out[u] = make_uint4(ka, ka != 0xFFFFFFFFu ? f2[ka & 0xFFFFu] : 0u, kb,
-                          kb != 0xFFFFFFFFu ? f2[kb & 0xFFFFu] : 0u);
+      for (int u = 0; u < ORBM_T; ++u) {
+        fk[u] = 0xFFFFFFFFu;
+        if (Lt[u] != 0xFFFFFFFFu) {
+          const uint32_t m = fmap[FP.f2 + (Lt[u] & 0xFFFFu)], hh = Lt[u] & 0xFFFF0000u;
+          Lt[u] = hh | (m & 0xFFFFu);
+          if ((m >> 16) != ORBM_NO_FOLLOWER) fk[u] = hh | (m >> 16);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < ORBM_T; ++u)
+        if (__ballot(fk[u] < Lt[ORBM_T - 1])) topk_insert(Lt, fk[u]);
+      full = Lt[ORBM_T - 1] != 0xFFFFFFFFu;
+    }
+    if (!act[t]) continue;
+    const int minD = Lt[0] != 0xFFFFFFFFu ? (int)(Lt[0] >> 16) : (1 << 20);
+    uint4 rec[ORBM_T / 2];
+    if (v1[t] && minD < P.th_low) {
+#pragma unroll
+      for (int u = 0; u < ORBM_T / 2; ++u) {
+        const uint32_t ka = Lt[2 * u], kb = Lt[2 * u + 1];
+        rec[u] = make_uint4(ka, ka != 0xFFFFFFFFu ? f2[ka & 0xFFFFu] : 0u, kb,
+                            kb != 0xFFFFFFFFu ? f2[kb & 0xFFFFu] : 0u);
+      }
+    }
+    // the row's record; FOLD: the follower's row gets the same under its own idx1
+    const bool twin = FOLD && fol1[t] != (int)ORBM_NO_FOLLOWER;
+    for (int w = 0; w < (FOLD ? 2 : 1); ++w) {
+      if (w == 1 && !twin) break;
+      const int pos = w ? fol1[t] : a[t];
+      const int i1 = w ? (int)P.feat1[NP.off1 + pos] : idx1[t];
+      const int r = NP.row_base + pos;
+      ev[r] = make_int2(-1, 0);
+      if (!v1[t]) {
+        rowinfo[r] = make_int4(0, 0, 0, i1);
+        continue;
+      }
+      rowinfo[r] = make_int4(1, full ? ORBM_T + 1 : 0, minD, i1);
+      if (minD >= P.th_low) continue;
+      uint4* out = reinterpret_cast<uint4*>(cand + (size_t)r * ORBM_T);
+#pragma unroll
+      for (int u = 0; u < ORBM_T / 2; ++u) out[u] = rec[u];
     }
   }
 }
-#define MC_INST(NK, RT, PK, CS) \
-  template __global__ void k_match_cand_mfma<NK, RT, PK, CS>(const MProblem*, const MNodePair*, const v4i_*, uint2*, int4*, int2*);
-MC_INST(6, MC_RT, false, 1)
-MC_INST(8, MC_RT, false, 1)
-MC_INST(6, 1, false, 4)
-MC_INST(8, 1, false, 4)
+#define MC_INST(NK, RT, PK, CS, FOLD)                                                                        \
+  template __global__ void k_match_cand_mfma<NK, RT, PK, CS, FOLD>(const MProblem*, const MNodePair*,       \
+                                                                   const v4i_*, uint2*, int4*, int2*,       \
+                                                                   const MFoldPair*, const uint32_t*);
+MC_INST(6, MC_RT, false, 1, false)
+MC_INST(8, MC_RT, false, 1, false)
+MC_INST(6, 1, false, 4, false)
+MC_INST(8, 1, false, 4, false)
 #if ORBM_FP4
-MC_INST(6, MC_RT, true, 1)
-MC_INST(8, MC_RT, true, 1)
-MC_INST(6, 1, true, 4)
-MC_INST(8, 1, true, 4)
+MC_INST(6, MC_RT, true, 1, false)
+MC_INST(8, MC_RT, true, 1, false)
+MC_INST(6, 1, true, 4, false)
+MC_INST(8, 1, true, 4, false)
+MC_INST(6, MC_RT, true, 1, true)
+MC_INST(8, MC_RT, true, 1, true)
+MC_INST(6, 1, true, 4, true)
+MC_INST(8, 1, true, 4, true)
 #endif
 #undef MC_INST
 
@@ -1446,14 +1525,19 @@ __global__ __launch_bounds__(256) void k_match_finalize(const MProblem* __restri
 }
 
 // the batched frame-pair matcher's tables (orbm_plan_match_frames): problem p
-// is frame pair p, one node pair over its two top-N selections
-__global__ void k_match_setup(MProblem* probs, MNodePair* nps, int npairs,
+// is frame pair p, one node pair over its two top-N selections.  List l's
+// selection is sel[l * topn ..] and its fold table fmap[l * topn ..]:
+// lists 2p (frame A) and 2p + 1 (frame B), or, when side B is side A one frame
+// back (shifted: frames 0 .. npairs in B's buffers), list f is frame f and
+// pair p takes lists p + 1 and p.
+__global__ void k_match_setup(MProblem* probs, MNodePair* nps, MFoldPair* fps, int npairs,
                               const orbx_keypoint* kps_a, const uint8_t* desc_a,
                               const orbx_keypoint* kps_b, const uint8_t* desc_b, int kcap,
-                              int topn, const uint32_t* sel, int32_t* match12, int* nmatches,
-                              float nnratio, int check_ori, int* last_off) {
+                              int topn, int shifted, const uint32_t* sel, int32_t* match12,
+                              int* nmatches, float nnratio, int check_ori, int* last_off) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npairs) return;
+  const int l1 = shifted ? p + 1 : 2 * p, l2 = shifted ? p : 2 * p + 1;
   MProblem P;
   P.desc1 = desc_a + (size_t)p * kcap * 32;
   P.desc2 = desc_b + (size_t)p * kcap * 32;
@@ -1461,8 +1545,8 @@ __global__ void k_match_setup(MProblem* probs, MNodePair* nps, int npairs,
   P.ang2 = &kps_b[(size_t)p * kcap].angle;
   P.valid1 = nullptr;
   P.valid2 = nullptr;
-  P.feat1 = sel + ((size_t)p * 2 + 0) * topn;
-  P.feat2 = sel + ((size_t)p * 2 + 1) * topn;
+  P.feat1 = sel + (size_t)l1 * topn;
+  P.feat2 = sel + (size_t)l2 * topn;
   P.match12 = match12 + (size_t)p * kcap;
   P.nmatches = nmatches + p;
   P.ang_stride = (int)(sizeof(orbx_keypoint) / sizeof(float));
@@ -1487,24 +1571,53 @@ __global__ void k_match_setup(MProblem* probs, MNodePair* nps, int npairs,
   NP.row_base = p * topn;
   NP.g2 = p * topn;
   nps[p] = NP;
+  MFoldPair FP;
+  FP.n1u = 0;
+  FP.n2u = 0;
+  FP.f1 = l1 * topn;
+  FP.f2 = l2 * topn;
+  fps[p] = FP;
   last_off[p] = p * kcap;
 }
 
 // ---------------------------------------------------------------------------
 // k_match_select: top-`topn` keypoints of one frame by (response desc,
-// index asc), written in ascending index order (one vocabulary node).
-// grid (npairs, 2): y = side (0: frame A -> list1, 1: frame B -> list2).
+// index asc), written in ascending index order (one vocabulary node), then
+// the list's fold table (hbits > 0).
+// grid (npairs, 2): y = side (0: frame A -> list1, 1: frame B -> list2), or
+// shifted (k_match_setup) grid (npairs + 1): frame x of side B's buffers is
+// list2 of pair x and list1 of pair x - 1, selected once.
+//
+// Fold (MFoldPair): entries claim the slot of their descriptor's hash
+// (match_fold_hash.h) in an LDS table by atomicMin of position << 16 | 0xFFFF;
+// an entry that finds another claimant compares all 32 bytes with it and, if
+// equal, bids for being its follower by atomicMin of claimant << 16 | position
+// on the same word: the follower is the copy with the smallest position after
+// the claimant's, further copies stay representatives without a follower.  An
+// entry whose bytes differ from its slot's claimant stays a representative:
+// a missed fold costs time only.
+// fst (topn dwords of this list; entry j is read and written by thread j & 255
+// alone): the entry's slot, | FS_DUP if it equals its slot's claimant, or
+// FS_LOSER if it lost its slot to other bytes.
 // ---------------------------------------------------------------------------
+#define FS_DUP 0x20000000u
+#define FS_LOSER 0x40000000u
 __global__ __launch_bounds__(256) void k_match_select(
-    MProblem* __restrict__ probs, MNodePair* __restrict__ nps, const orbx_keypoint* __restrict__ kps_a,
+    MProblem* __restrict__ probs, MNodePair* __restrict__ nps, MFoldPair* __restrict__ fps,
+    const orbx_keypoint* __restrict__ kps_a, const uint8_t* __restrict__ desc_a,
     const int* __restrict__ count_a, const orbx_keypoint* __restrict__ kps_b,
-    const int* __restrict__ count_b, int kcap, int topn, uint32_t* __restrict__ sel) {
+    const uint8_t* __restrict__ desc_b, const int* __restrict__ count_b, int kcap, int topn,
+    int shifted, int hbits, uint32_t* __restrict__ sel, uint32_t* __restrict__ fmap,
+    uint32_t* __restrict__ fst) {
+  extern __shared__ uint32_t fold_lds[];
   __shared__ int hist[256];
   __shared__ int s_R, s_above, wtot[4];
-  const int p = blockIdx.x, side = blockIdx.y, tid = threadIdx.x;
+  const int p = blockIdx.x, side = shifted ? 1 : blockIdx.y, tid = threadIdx.x;
+  const int list = shifted ? p : 2 * p + side;
   const orbx_keypoint* kp = (side ? kps_b : kps_a) + (size_t)p * kcap;
+  const uint8_t* desc = (side ? desc_b : desc_a) + (size_t)p * kcap * 32;
   const int K = side ? count_b[p] : count_a[p];
-  uint32_t* out = sel + ((size_t)p * 2 + side) * topn;
+  uint32_t* out = sel + (size_t)list * topn;
   hist[tid] = 0;
   // the first SEL_U blocks of 256 responses stay in registers for the
   // selection pass below (all loads issued at once; no reload per block)
@@ -1582,9 +1695,126 @@ __global__ __launch_bounds__(256) void k_match_select(
   for (int u = 0; u < SEL_U; ++u)
     if (256 * u < K) block(256 * u, rr[u]);
   for (int base = 256 * SEL_U; base < K; base += 256) block(base, base + tid < K ? (int)kp[base + tid].response : -2);
+
+  // the fold table of the list out[0 .. nsel).  Every pass takes FU blocks of
+  // 256 entries at once with all loads of a step issued together: a pass costs
+  // a few load latencies, not a few per block
+  int nrep = nsel;
+  if (hbits > 0 && nsel > 0) {
+    constexpr int FU = 4;
+    __shared__ int wt[FU][4];
+    uint32_t* T = fold_lds;  // slot -> claimant << 16 | its follower (0xFFFF: none)
+    uint32_t* st = fst + (size_t)list * topn;
+    uint32_t* fm = fmap + (size_t)list * topn;
+    const uint4* dq = reinterpret_cast<const uint4*>(desc);
+    for (int i = tid; i < (1 << hbits); i += 256) T[i] = 0xFFFFFFFFu;
+    __syncthreads();  // also: this block's out[] writes are visible to it
+    // claims
+    for (int b0 = 0; b0 < nsel; b0 += 256 * FU) {
+      uint32_t idx[FU];
+      uint4 q0[FU], q1[FU];
+#pragma unroll
+      for (int u = 0; u < FU; ++u) idx[u] = out[min(b0 + tid + 256 * u, nsel - 1)];
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        q0[u] = dq[(size_t)idx[u] * 2];
+        q1[u] = dq[(size_t)idx[u] * 2 + 1];
+      }
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        const int j = b0 + tid + 256 * u;
+        if (j >= nsel) continue;
+        const uint32_t w[8] = {q0[u].x, q0[u].y, q0[u].z, q0[u].w, q1[u].x, q1[u].y, q1[u].z, q1[u].w};
+        const uint32_t s = orbm_fold_slot(w, 0, hbits);
+        atomicMin(&T[s], ((uint32_t)j << 16) | ORBM_NO_FOLLOWER);
+        st[j] = s;
+      }
+    }
+    __syncthreads();
+    // an entry that is not its slot's claimant: it bids for being the
+    // claimant's follower if all 32 bytes agree, else it is a loser
+    for (int b0 = 0; b0 < nsel; b0 += 256 * FU) {
+      int c[FU];
+      uint32_t s[FU], idx[FU], idc[FU];
+      uint4 q0[FU], q1[FU], c0[FU], c1[FU];
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        const int j = b0 + tid + 256 * u;
+        s[u] = 0;
+        idx[u] = 0;
+        if (j < nsel) {
+          s[u] = st[j];
+          idx[u] = out[j];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        const int j = b0 + tid + 256 * u;
+        c[u] = j < nsel ? (int)(T[s[u]] >> 16) : j;
+        idc[u] = j < nsel ? out[c[u]] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        q0[u] = dq[(size_t)idx[u] * 2];
+        q1[u] = dq[(size_t)idx[u] * 2 + 1];
+        c0[u] = dq[(size_t)idc[u] * 2];
+        c1[u] = dq[(size_t)idc[u] * 2 + 1];
+      }
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        const int j = b0 + tid + 256 * u;
+        if (c[u] == j) continue;  // the claimant itself, or past the list
+        const uint32_t diff = (q0[u].x ^ c0[u].x) | (q0[u].y ^ c0[u].y) | (q0[u].z ^ c0[u].z) |
+                              (q0[u].w ^ c0[u].w) | (q1[u].x ^ c1[u].x) | (q1[u].y ^ c1[u].y) |
+                              (q1[u].z ^ c1[u].z) | (q1[u].w ^ c1[u].w);
+        if (diff == 0) {
+          atomicMin(&T[s[u]], ((uint32_t)c[u] << 16) | (uint32_t)j);
+          st[j] = s[u] | FS_DUP;
+        } else {
+          st[j] = FS_LOSER;
+        }
+      }
+    }
+    __syncthreads();
+    // representatives in position order: everything but the bids that won
+    nrep = 0;
+    for (int b0 = 0; b0 < nsel; b0 += 256 * FU) {  // workgroup-uniform trip count
+      uint32_t fol[FU];  // the representative's follower, or FS_DUP: a follower itself
+      uint64_t mr[FU];
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        const int j = b0 + tid + 256 * u;
+        fol[u] = FS_DUP;
+        if (j < nsel) {
+          const uint32_t s = st[j];
+          fol[u] = ORBM_NO_FOLLOWER;
+          if (s != FS_LOSER) {
+            const uint32_t t = T[s & ~FS_DUP] & 0xFFFFu;
+            if (!(s & FS_DUP)) fol[u] = t;
+            else if (t == (uint32_t)j) fol[u] = FS_DUP;
+          }
+        }
+        mr[u] = __ballot(fol[u] != FS_DUP);
+        if (lane == 0) wt[u][wave] = __popcll(mr[u]);
+      }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < FU; ++u) {
+        int off = nrep;
+        for (int w = 0; w < wave; ++w) off += wt[u][w];
+        if (fol[u] != FS_DUP)
+          fm[off + __popcll(mr[u] & ((1ull << lane) - 1ull))] = (uint32_t)(b0 + tid + 256 * u) | (fol[u] << 16);
+        nrep += wt[u][0] + wt[u][1] + wt[u][2] + wt[u][3];
+      }
+      __syncthreads();
+    }
+  }
   if (tid == 0) {
-    if (side == 0) { nps[p].n1 = nsel; probs[p].n1 = K; }
-    else { nps[p].n2 = nsel; probs[p].n2 = K; }
+    // list1 of one pair and / or list2 of another
+    const int p1 = shifted ? p - 1 : (side == 0 ? p : -1);
+    const int p2 = shifted ? (p < (int)gridDim.x - 1 ? p : -1) : (side == 1 ? p : -1);
+    if (p1 >= 0) { nps[p1].n1 = nsel; probs[p1].n1 = K; fps[p1].n1u = nrep; }
+    if (p2 >= 0) { nps[p2].n2 = nsel; probs[p2].n2 = K; fps[p2].n2u = nrep; }
   }
 }
 

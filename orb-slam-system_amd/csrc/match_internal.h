@@ -96,4 +96,17 @@ struct MNodePair {
   int g2;        /* list2 position j's descriptor is gdesc2[g2 + j] (k_match_gather2) */
 };
 
+/* Folded lists of a node pair (batched plan only, beside nps[]): entries of a
+ * list with byte-identical descriptors, in pairs, are one representative (the
+ * smaller list position) and its follower.  fmap[f + u] = position of the
+ * list's u-th representative, in ascending position order, | its follower's
+ * position << 16 (ORBM_NO_FOLLOWER: none).  k_match_expand2 and
+ * k_match_cand_mfma's FOLD forms run over representatives only; n1 / n2, rows,
+ * positions in keys and feature indices stay those of the whole lists. */
+#define ORBM_NO_FOLLOWER 0xFFFFu
+struct MFoldPair {
+  int n1u, n2u; /* representatives of list1 / list2 */
+  int f1, f2;   /* their tables in fmap */
+};
+
 #endif

@@ -46,7 +46,7 @@ assert KEYPOINT_DTYPE.itemsize == 28
 OK, ERR_ARG, ERR_CELL_ROI, ERR_LEVEL_SIZE, ERR_QUADTREE, ERR_CAPACITY, ERR_UNSUPPORTED, \
     ERR_HIP, ERR_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ORBV_QUERY_GATED = 1  # orbv_db_query_batch flags (include/orbx.h)
-ORBM_PLAN_ZERO_TAIL, ORBM_PLAN_VALU = 1, 2  # orbm_plan_set_options flags (include/orbx.h)
+ORBM_PLAN_ZERO_TAIL, ORBM_PLAN_VALU, ORBM_PLAN_NO_FOLD = 1, 2, 4  # orbm_plan_set_options flags (include/orbx.h)
 ORBX_PLAN_PYR_TILES, ORBX_PLAN_BRIEF_PATCH, ORBX_PLAN_BRIEF_LEVEL, ORBX_PLAN_FAST_DENSE = 1, 8, 16, 64  # orbx_plan_set_options flags
 ORBX_PLAN_NO_TWINS = 128
 
@@ -61,6 +61,7 @@ EXPORTED = [
     "orbx_plan_stage_times", "orbx_synth_frames", "orbm_search_by_bow", "orbm_search_by_bow_kf_frame",
     "orbm_descriptor_distance_batch", "orbm_plan_create", "orbm_plan_destroy",
     "orbm_plan_match_frames", "orbm_plan_set_timing", "orbm_plan_stage_times", "orbm_plan_set_options",
+    "orbm_plan_fold_stats",
     "orbx_stereo_match", "orbs_plan_create", "orbs_plan_destroy", "orbs_plan_match",
     "orbs_plan_check", "orbs_plan_set_timing", "orbs_plan_stage_times",
     "orbv_vocab_load_text", "orbv_vocab_create", "orbv_vocab_destroy", "orbv_vocab_info",
@@ -311,6 +312,7 @@ _sig = {
     "orbm_plan_set_timing": (I, [P, I]),
     "orbm_plan_set_options": (I, [P, I]),
     "orbm_plan_stage_times": (I, [P, P, P, I]),
+    "orbm_plan_fold_stats": (I, [P, P]),
     "orbx_stereo_match": (I, [P, P, P, P, I, P, P, I, F, F, P, P, P]),
     "orbs_plan_create": (I, [P, I, P]),
     "orbs_plan_destroy": (I, [P]),
@@ -1554,16 +1556,19 @@ class MatchPlan:
 
     zero_tail=True asserts that bytes 24..31 of every descriptor are zero (true
     of Plan.extract outputs) and lets the distance kernels skip them; valu=True
-    takes the xor/popcount distance kernel instead of the MFMA one."""
+    takes the xor/popcount distance kernel instead of the MFMA one; fold=False
+    gives every selected keypoint its own distance row and column instead of
+    computing byte-identical descriptors of a list once (same matches)."""
 
-    def __init__(self, max_pairs, kcap, topn=2000, device=0, zero_tail=False, valu=False):
+    def __init__(self, max_pairs, kcap, topn=2000, device=0, zero_tail=False, valu=False, fold=True):
         import torch
         h = ctypes.c_void_p()
         _check(_lib.orbm_plan_create(max_pairs, kcap, topn, device, ctypes.byref(h)),
                "orbm_plan_create")
         self._h, self.kcap, self.topn, self.max_pairs = h, kcap, topn, max_pairs
         _check(_lib.orbm_plan_set_options(h, (ORBM_PLAN_ZERO_TAIL if zero_tail else 0)
-                                          | (ORBM_PLAN_VALU if valu else 0)), "orbm_plan_set_options")
+                                          | (ORBM_PLAN_VALU if valu else 0)
+                                          | (0 if fold else ORBM_PLAN_NO_FOLD)), "orbm_plan_set_options")
         dev = torch.device("cuda", device)
         self.match12 = torch.empty((max_pairs, kcap), dtype=torch.int32, device=dev)
         self.nmatches = torch.zeros(max_pairs, dtype=torch.int32, device=dev)
@@ -1590,6 +1595,13 @@ class MatchPlan:
                                            cnt_b.data_ptr(), float(nnratio), 1 if check_ori else 0,
                                            m.data_ptr(), nm.data_ptr(), _stream_handle(stream)),
                "orbm_plan_match_frames")
+
+    def fold_stats(self):
+        """(list1 entries, list1 followers, list2 entries, list2 followers) of the
+        last match() call, summed over its pairs; waits for that call."""
+        out = np.zeros(4, np.int64)
+        _check(_lib.orbm_plan_fold_stats(self._h, _p(out)), "orbm_plan_fold_stats")
+        return tuple(int(v) for v in out)
 
     def set_timing(self, enable):
         _check(_lib.orbm_plan_set_timing(self._h, 1 if enable else 0))
