@@ -4,15 +4,13 @@ ctypes), the random and planted BowVectors, other summation orders of the same
 terms, and the non-vacuity checks.  No GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "bowdb_ref.c")
+import native
+from native import ROOT, ptr as _ptr  # noqa: F401
+
 SCORINGS = (0, 1, 2, 5)  # L1_NORM, L2_NORM, CHI_SQUARE, DOT_PRODUCT
 NWORDS = 1000            # synth.vocabulary(k=10, L=3)
 # seeds of planted_order_pair's inexact terms, per scoring: the first for which
@@ -20,16 +18,9 @@ NWORDS = 1000            # synth.vocabulary(k=10, L=3)
 PLANT_SEED = {0: 0, 1: 182, 2: 2, 5: 0}  # L2's closing sqrt hides most one-ulp differences of the sum
 
 
-def _ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="bowdb_ref_")
-    so = os.path.join(d, "libbowdbref.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("bowdb_ref.c")
     vp, ci, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64
     lib.bowref_score.restype, lib.bowref_score.argtypes = ctypes.c_double, [ci, vp, vp, ci, vp, vp, ci]
     lib.bowref_terms.restype, lib.bowref_terms.argtypes = ci, [ci, vp, vp, ci, vp, vp, ci, vp]

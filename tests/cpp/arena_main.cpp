@@ -12,19 +12,11 @@
 #include <vector>
 
 #include "call_arena.h"
+#include "expect.h"
 
 using orbx::CallArena;
 using orbx::CallWs;
 using orbx::Slot;
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
 
 static const size_t kCounts[] = {0, 1, 7, 300};
 enum { NC = 4 };

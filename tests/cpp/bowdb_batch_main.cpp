@@ -11,17 +11,9 @@
 #include <vector>
 
 #include "bowdb_internal.h"
+#include "expect.h"
 
 using namespace orbx;
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
 
 enum { OK = 0, ERR_ARG = -1, ERR_UNSUPPORTED = -6 };
 static const uint32_t NWORDS = 10000;

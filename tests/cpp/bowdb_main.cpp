@@ -15,17 +15,9 @@
 #include <vector>
 
 #include "bowdb_internal.h"
+#include "expect.h"
 
 using namespace orbx;
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
 
 struct Model {
   std::vector<uint32_t> word;

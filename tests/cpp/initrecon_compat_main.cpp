@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "orbslam2_compat.hpp"
+#include "expect.h"
 
 extern "C" int ir_ref_initialize(int n1, const float* keys1, int n2, const float* keys2, int kstride,
                                  const int32_t* match12, int nit, const int32_t* sets, float sigma, float* H21,
@@ -27,15 +28,6 @@ struct Frame {
   cv::Mat mK;
   std::vector<cv::KeyPoint> mvKeysUn;
 };
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
 
 static uint32_t lcg_state = 2468;
 static double uni(double a, double b) {

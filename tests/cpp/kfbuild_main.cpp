@@ -10,15 +10,7 @@
 #include <vector>
 
 #include "orbx.h"
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
+#include "expect.h"
 
 int main() {
   orbx_kf_camera cam;

@@ -13,15 +13,7 @@
 #include <vector>
 
 #include "owned.h"
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
+#include "expect.h"
 
 static int g_made = 0, g_freed = 0;
 static void counting_free(char* p) {

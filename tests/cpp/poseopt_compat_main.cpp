@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "poseopt_mocks.hpp"
+#include "expect.h"
 
 extern "C" {
 typedef struct {
@@ -22,15 +23,6 @@ int po_pose_optimization(const float Tcw[12], const float intr[5], int nlevels, 
 }
 
 using namespace ORB_SLAM2;
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;
 static double uni() {  // [0, 1)

@@ -13,6 +13,7 @@
 #include <set>
 
 #include "projbuild_mocks.hpp"
+#include "expect.h"
 
 extern "C" {
 typedef struct {
@@ -31,15 +32,6 @@ void pb_project(int mode, const pb_camera* C, const pb_points* P, int npts, floa
 }
 
 using namespace ORB_SLAM2;
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ull;
 static double uni() {  // [0, 1)

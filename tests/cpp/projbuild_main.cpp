@@ -14,15 +14,7 @@
 
 #include "orbx.h"
 #include "projbuild_internal.h"
-
-static int fails = 0;
-#define EXPECT(cond)                                                  \
-  do {                                                                \
-    if (!(cond)) {                                                    \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
+#include "expect.h"
 
 static float prev_float(float v) { return nextafterf(v, -INFINITY); }
 

@@ -11,15 +11,7 @@
 #include <vector>
 
 #include "orbx.h"
-
-static int fails = 0;
-#define EXPECT(cond)                                            \
-  do {                                                          \
-    if (!(cond)) {                                              \
-      fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++fails;                                                  \
-    }                                                           \
-  } while (0)
+#include "expect.h"
 
 int main() {
   // 1. geometry + tables + LUTs over a sweep of sizes and parameter sets

@@ -4,17 +4,13 @@ process with gcc and loaded with ctypes), the seeded scene generator, the set
 draw and the planted cases.  No GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "initransac_ref.c")
+import native
+from native import KEYPOINT_DTYPE, ROOT, same_bits, ptr as _ptr  # noqa: F401
+
 f32 = np.float32
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                           ("octave", "<i4"), ("class_id", "<i4")])
 KSTRIDE = KEYPOINT_DTYPE.itemsize // 4
 COUNTERS = ("h_sweeps", "h_sweeps_max", "h_capped", "h_converged", "f_sweeps", "f_sweeps_max", "f_capped",
             "f_converged", "f3_sweeps", "f3_sweeps_max", "f3_capped", "f3_converged", "rotations", "skipped_orth",
@@ -29,10 +25,7 @@ IR_SWEEPS = 30  # csrc/initransac_math.h
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="ir_ref_")
-    so = os.path.join(d, "libirref.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("initransac_ref.c")
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     lib.ir_ref_initialize.restype = ci
     lib.ir_ref_initialize.argtypes = [ci, vp, ci, vp, ci, vp, ci, vp, cf] + [vp] * 9
@@ -43,10 +36,6 @@ def ref_lib():
     lib.ir_ref_inv3.restype = None
     lib.ir_ref_inv3.argtypes = [vp, vp]
     return lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def make_keys(u, v):
@@ -206,13 +195,6 @@ def scene_ref(kind, nmatch, seed, nit=60, **kw):
         pair, _ = scene(kind, nmatch, seed, nit, **kw)
         _REF_CACHE[key] = ref_initialize(pair, nit)
     return _REF_CACHE[key]
-
-
-def same_bits(a, b):
-    """bit-for-bit equality of two float32 arrays, NaNs of any payload equal"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
 
 
 def same_result(got, ref):

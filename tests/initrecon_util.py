@@ -4,16 +4,13 @@ process with gcc and loaded with ctypes), two-view scenes with a known R, t and
 points, and the planted cases.  No GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import native
+from native import ROOT, ptr as _ptr  # noqa: F401
 from initransac_util import KEYPOINT_DTYPE, KSTRIDE, make_keys, match_list, same_bits  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "initrecon_ref.c")
 f32 = np.float32
 H, F, AUTO = 0, 1, 2  # ORBX_RECON_*
 SIGMA, MIN_PARALLAX, MIN_TRIANGULATED = 1.0, 1.0, 50  # Initialize :74-76
@@ -34,11 +31,7 @@ COUNTERS = (("absent", "early_exit") + BRANCHES + H_OUT + F_OUT +
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="rc_ref_")
-    so = os.path.join(d, "librcref.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-strict-aliasing", "-fPIC", "-shared", "-Wall",
-                           "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("initrecon_ref.c")
     vp, ci, cf, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double
     lib.rc_ref_reconstruct.restype = ci
     lib.rc_ref_reconstruct.argtypes = [ci, vp, ci, vp, ci, vp, vp, ci, ci, vp, vp, cf, cf, ci] + [vp] * 7
@@ -57,10 +50,6 @@ def ref_lib():
     lib.rc_ref_unkey.argtypes = [ctypes.c_uint32]
     assert lib.rc_ref_ncounters() == len(COUNTERS)
     return lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def ransac_record(H21=None, F21=None, RH=0.5, nmatch=0):

@@ -4,16 +4,13 @@ ctypes), an independent brute force in numpy and the planted frames.  No GPU,
 no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import native
+from native import ROOT  # noqa: F401
 from kfwindow_util import COLS, H, KEYPOINT_DTYPE, ROWS, W, Frame, flip, frame_dict, _ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "initsearch_ref.c")
 TH_LOW = 50
 INT_MAX = 2 ** 31 - 1
 STAT_NAMES = ("accepted", "displaced", "filter_changed", "ratio_rejected", "rot_removed", "stale", "nlow")
@@ -21,10 +18,7 @@ STAT_NAMES = ("accepted", "displaced", "filter_changed", "ratio_rejected", "rot_
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="ini_ref_")
-    so = os.path.join(d, "libiniref.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("initsearch_ref.c")
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.ini_search.restype = ci
     lib.ini_search.argtypes = [vp, vp, vp, vp, ci, ctypes.c_float, ci, ci, vp, vp]

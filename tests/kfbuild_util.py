@@ -4,17 +4,14 @@ gcc and loaded with ctypes), the random scenes and the planted edge cases.  No
 GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import native
+from native import ROOT, ptr as _ptr  # noqa: F401
 from kfwindow_util import H, KF_QUERY_DTYPE, W
 from projbuild_util import _rotation, down, log_scale_factor, scale_factors, up
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "kfbuild_ref.c")
 f32 = np.float32
 MAX_LEVELS = 32
 FUSE, SIM3 = 1, 2
@@ -45,19 +42,12 @@ class RefPoints(ctypes.Structure):
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="kb_ref_")
-    so = os.path.join(d, "libkbref.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("kfbuild_ref.c")
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     lib.kb_project.restype = None
     lib.kb_project.argtypes = [ci, ci, vp, vp, ci, ctypes.c_int32, cf, vp, vp, vp, vp]
     lib.kb_predict_scale.restype, lib.kb_predict_scale.argtypes = ci, [cf, cf, cf, ci]
     return lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def make_camera(R, t, ow, sR21, t21, fx, fy, cx, cy, bounds, scale=1.2, nlevels=8):

@@ -5,17 +5,12 @@ a keyframe's own features plus noise with descriptors a few bits off, decoys,
 exact duplicates, border and off-gate queries).  No GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "kfwindow_ref.c")
+import native
+from native import KEYPOINT_DTYPE, ROOT, ptr as _ptr  # noqa: F401
 
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
-                           ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 KF_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("radius", "<f4"), ("level", "<i4"),
                            ("desc", "<i4")])
 INT_MAX = 2 ** 31 - 1
@@ -32,11 +27,7 @@ class Frame(ctypes.Structure):  # kfw_frame == orbx_kf_frame
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="kfw_ref_")
-    so = os.path.join(d, "libkfwref.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so,
-                           SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("kfwindow_ref.c")
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.kfw_grid_create.restype, lib.kfw_grid_create.argtypes = vp, [vp]
     lib.kfw_grid_free.restype, lib.kfw_grid_free.argtypes = None, [vp]
@@ -45,10 +36,6 @@ def ref_lib():
     lib.kfw_grid_cell_of.restype, lib.kfw_grid_cell_of.argtypes = None, [vp, ci, vp]
     lib.kfw_descriptor_distance.restype, lib.kfw_descriptor_distance.argtypes = ci, [vp, vp]
     return lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _struct(k, keep):

@@ -4,19 +4,15 @@ with gcc and loaded with ctypes), the seeded scene generator and the planted
 cases.  No GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "poseopt_ref.c")
+import native
+from native import KEYPOINT_DTYPE, ROOT, same_bits, ptr as _ptr  # noqa: F401
+
 f32 = np.float32
 SEQUENTIAL, DEVICE = 0, 1
 PO_T = 256  # csrc/poseopt_math.h
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                           ("octave", "<i4"), ("class_id", "<i4")])
 COUNTERS = ("accepted", "rejected", "solver_fail", "end_iters", "end_qmax", "end_rho0", "end_small", "rounds",
             "no_active", "readmitted", "invalid")
 # n of the size sweep: the return-0 sizes, the one-round sizes, wavefront and
@@ -28,18 +24,11 @@ WIDTH, HEIGHT = 1241, 376
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="po_ref_")
-    so = os.path.join(d, "libporef.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("poseopt_ref.c")
     vp, ci = ctypes.c_void_p, ctypes.c_int
     lib.po_pose_optimization.restype = ci
     lib.po_pose_optimization.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     return lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def inv_level_sigma2(scale=1.2, nlevels=8):
@@ -200,13 +189,6 @@ OUTLIER_SCENE = dict(noise=0.5, outliers=0.2)
 def sweep_scene(n, seed=11):
     """the GPU size sweep's problem of n features: mixed, planted outliers"""
     return scene(n, seed + n, **OUTLIER_SCENE)
-
-
-def same_bits(a, b):
-    """bit-for-bit equality of two float32 arrays, NaNs of any payload equal"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
 
 
 # --------------------------------------------------------------------------- semantics cases

@@ -4,16 +4,13 @@ process with gcc and loaded with ctypes), the random scenes and the planted
 edge cases.  No GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import native
+from native import ROOT, ptr as _ptr  # noqa: F401
 from projection_util import PROJ_QUERY_DTYPE, geometry
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "projbuild_ref.c")
 f32 = np.float32
 MAX_LEVELS = 32
 POINT_FIELDS = ("pos", "normal", "min_dist_inv", "max_dist_inv", "max_dist", "octave", "angle", "skip")
@@ -44,19 +41,12 @@ class RefPoints(ctypes.Structure):
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="pb_ref_")
-    so = os.path.join(d, "libpbref.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("projbuild_ref.c")
     vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
     lib.pb_project.restype = None
     lib.pb_project.argtypes = [ci, vp, vp, ci, cf, cf, ci, vp, vp, vp, vp, vp]
     lib.pb_predict_scale.restype, lib.pb_predict_scale.argtypes = ci, [cf, cf, cf, ci]
     return lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def scale_factors(scale, nlevels):

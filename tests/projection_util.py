@@ -10,8 +10,8 @@ import functools
 
 import numpy as np
 
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
-                           ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
+from native import KEYPOINT_DTYPE  # noqa: F401
+
 PROJ_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("radius", "<f4"), ("min_level", "<i4"),
                              ("max_level", "<i4"), ("xr", "<f4"), ("angle", "<f4")])
 

@@ -25,9 +25,9 @@ import math
 
 import numpy as np
 
+from native import KEYPOINT_DTYPE  # noqa: F401
+
 F = np.float32
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
-                           ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 TH_HIGH, TH_LOW = 100, 50
 W, H, NF, NLEVELS = 640, 480, 1000, 8  # every planted frame but the tall one
 FX, BF = 435.2, 386.1448

@@ -4,15 +4,11 @@ scoring in exact rational arithmetic, the (smallest common word, add sequence)
 order claim of orbv_db_query against the restatement's literal per-word lists,
 and the host ASan/UBSan run of the store's bookkeeping
 (csrc/bowdb_internal.h, tests/cpp/bowdb_main.cpp)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import bowdb_util as U
-
-PKG = os.path.join(U.ROOT, "orb-slam-system_amd")
+import native
 
 
 @pytest.mark.parametrize("scoring", U.SCORINGS)
@@ -102,11 +98,5 @@ def test_order_is_smallest_common_word_then_add_sequence(seed):
 
 
 def test_store_bookkeeping_clean_under_asan_ubsan():
-    subprocess.check_call(["make", "-s", "-C", PKG, "build_asan/bowdb_main"], timeout=600)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([os.path.join(PKG, "build_asan", "bowdb_main")], env=env, capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = native.run_sanitized("bowdb_main")
     assert "0 failures" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

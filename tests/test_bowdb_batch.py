@@ -4,27 +4,17 @@ packing (csrc/bowdb_internal.h, tests/cpp/bowdb_batch_main.cpp), and the claim
 the order kernel rests on, against the restatement's literal per-word lists:
 sorting a query's sharing keyframes by (rank of the smallest common word in the
 query, add position) reproduces the list."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import bowdb_util as U
+import native
 import test_bowdb as B  # the histories' order statement, imported and not edited
-
-PKG = os.path.join(U.ROOT, "orb-slam-system_amd")
 
 
 def test_batch_host_pieces_clean_under_asan_ubsan():
-    subprocess.check_call(["make", "-s", "-C", PKG, "build_asan/bowdb_batch_main"], timeout=600)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([os.path.join(PKG, "build_asan", "bowdb_batch_main")], env=env, capture_output=True,
-                       text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = native.run_sanitized("bowdb_batch_main")
     assert "0 failures" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 
 def _rank_order(history, query):

@@ -9,27 +9,21 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
-CPP = os.path.join(ROOT, "tests", "cpp")
+import native
 
 
-def _build(tmp_path):
-    exe = tmp_path / "bowdb_batch_compat_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unused-function", "-I", os.path.join(PKG, "cpp"),
-                           "-I", CPP, os.path.join(CPP, "bowdb_batch_compat_main.cpp"), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("bowdb_batch_compat_main.cpp", extra=("-Wno-unused-function",))
 
 
-def test_batched_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_batched_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 @pytest.mark.gpu
 def test_batched_relocalization_equals_the_single_calls(gpu, tmp_path):
     out = tmp_path / "out.txt"
-    subprocess.check_call([str(_build(tmp_path)), "7", str(out), str(tmp_path / "voc.txt")], timeout=120)
+    subprocess.check_call([_build(), "7", str(out), str(tmp_path / "voc.txt")], timeout=120)
     got = {"H": [], "D": [], "X": {}}
     for line in out.read_text().split("\n"):
         w = line.split()

@@ -10,23 +10,18 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
-CPP = os.path.join(ROOT, "tests", "cpp")
+import native
+
 PLANTED = "3e800000"  # 0.25f, what mLoopScore / mRelocScore start at
 
 
-def _build(tmp_path):
-    exe = tmp_path / "bowdb_compat_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(PKG, "cpp"), "-I", CPP,
-                           os.path.join(CPP, "bowdb_compat_main.cpp"), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("bowdb_compat_main.cpp")
 
 
 def _run(exe, tmp_path, *mode):
     out = tmp_path / "out.txt"
-    subprocess.check_call([str(exe), "7", str(out), str(tmp_path / "voc.txt")] + list(mode), timeout=120)
+    subprocess.check_call([exe, "7", str(out), str(tmp_path / "voc.txt")] + list(mode), timeout=120)
     got = {"H": [], "D": [], "X": []}
     for line in out.read_text().split("\n"):
         w = line.split()
@@ -67,19 +62,19 @@ def _host_loop_conditions(H, X):
     return ret
 
 
-def test_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 def test_host_loop_contains_every_quirk(tmp_path):
-    got = _run(_build(tmp_path), tmp_path, "host")  # the host loop alone: no GPU
+    got = _run(_build(), tmp_path, "host")  # the host loop alone: no GPU
     assert not got["D"]
     _host_loop_conditions(got["H"], got["X"])
 
 
 @pytest.mark.gpu
 def test_compat_database_equals_the_host_loop(gpu, tmp_path):
-    got = _run(_build(tmp_path), tmp_path)
+    got = _run(_build(), tmp_path)
     H, D, X = got["H"], got["D"], got["X"]
     _host_loop_conditions(H, X)
     assert ("0", "SCORE", "differ", "0") in X  # ORBVocabulary::score, single and batched

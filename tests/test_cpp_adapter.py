@@ -8,33 +8,27 @@ import subprocess
 import numpy as np
 import pytest
 
+import native
 from orbx import synth
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
+
+def _build_stereo():
+    return native.program("stereo_main.cpp")
 
 
-def _build_stereo(tmp_path):
-    exe = tmp_path / "stereo_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(PKG, "cpp"),
-                           os.path.join(ROOT, "tests", "cpp", "stereo_main.cpp"), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
-
-
-def test_cpp_stereo_adapter_compiles(tmp_path):
-    assert _build_stereo(tmp_path).exists()
+def test_cpp_stereo_adapter_compiles():
+    assert os.path.exists(_build_stereo())
 
 
 @pytest.mark.gpu
 def test_cpp_stereo_adapter_matches_oracle(gpu, oracle, tmp_path):
-    exe = _build_stereo(tmp_path)
+    exe = _build_stereo()
     W, H, nf, fx, bf = 1241, 376, 2000, 718.856, 386.1448
     L, R = synth.stereo_pair(W, H, 60)
     (tmp_path / "l.raw").write_bytes(L.tobytes())
     (tmp_path / "r.raw").write_bytes(R.tobytes())
     out = tmp_path / "out.bin"
-    subprocess.check_call([str(exe), str(tmp_path / "l.raw"), str(tmp_path / "r.raw"), str(W),
+    subprocess.check_call([exe, str(tmp_path / "l.raw"), str(tmp_path / "r.raw"), str(W),
                            str(H), str(nf), repr(fx), repr(bf), str(out)])
     raw = out.read_bytes()
     nl, nr, n = np.frombuffer(raw[:12], np.int32).tolist()
@@ -54,21 +48,17 @@ def test_cpp_stereo_adapter_matches_oracle(gpu, oracle, tmp_path):
     assert np.array_equal(dep.view(np.uint32), dep0.view(np.uint32))
 
 
-def _build_vocab(tmp_path):
-    exe = tmp_path / "vocab_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(PKG, "cpp"),
-                           os.path.join(ROOT, "tests", "cpp", "vocab_main.cpp"), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
+def _build_vocab():
+    return native.program("vocab_main.cpp")
 
 
-def test_cpp_vocab_adapter_compiles(tmp_path):
-    assert _build_vocab(tmp_path).exists()
+def test_cpp_vocab_adapter_compiles():
+    assert os.path.exists(_build_vocab())
 
 
 @pytest.mark.gpu
 def test_cpp_vocab_adapter_matches_oracle(gpu, oracle, tmp_path):
-    exe = _build_vocab(tmp_path)
+    exe = _build_vocab()
     W, H = 1241, 376
     voc = synth.vocabulary(10, 5, seed=3)
     synth.write_vocabulary_text(tmp_path / "voc.txt", voc)
@@ -76,7 +66,7 @@ def test_cpp_vocab_adapter_matches_oracle(gpu, oracle, tmp_path):
     (tmp_path / "a.raw").write_bytes(a.tobytes())
     (tmp_path / "b.raw").write_bytes(b.tobytes())
     out = tmp_path / "out.bin"
-    subprocess.check_call([str(exe), str(tmp_path / "voc.txt"), str(tmp_path / "a.raw"),
+    subprocess.check_call([exe, str(tmp_path / "voc.txt"), str(tmp_path / "a.raw"),
                            str(tmp_path / "b.raw"), str(W), str(H), str(out)])
     raw = out.read_bytes()
     n1, nb, nf, nm = np.frombuffer(raw[:16], np.int32).tolist()
@@ -104,19 +94,15 @@ def test_cpp_vocab_adapter_matches_oracle(gpu, oracle, tmp_path):
     assert nm == rnm and np.array_equal(m12, np.where(rm >= 0, rm, -1))
 
 
-def _build_compat(tmp_path):
-    exe = tmp_path / "compat_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-I",
-                           os.path.join(PKG, "cpp"), os.path.join(ROOT, "tests", "cpp", "compat_main.cpp"),
-                           "-o", str(exe), "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
+def _build_compat():
+    return native.program("compat_main.cpp", extra=("-pthread",))
 
 
-def test_reference_shaped_call_sites_compile(tmp_path):
+def test_reference_shaped_call_sites_compile():
     """Frame::ExtractORB / Frame::Frame's stereo threads / LoopClosing's
     SearchByBoW / DescriptorDistance(cv::Mat, cv::Mat) written as in the
     reference compile against cpp/orbslam2_compat.hpp."""
-    assert _build_compat(tmp_path).exists()
+    assert os.path.exists(_build_compat())
 
 
 def _compat_featvec(n):
@@ -134,7 +120,7 @@ def test_reference_shaped_concurrent_call_sites(gpu, oracle, tmp_path):
     Frame-shaped constructor, concurrently with SearchByBoW(KF, KF) on a third
     thread, 6 repetitions (each identical to the first, checked in C++), all
     bit-exact against the oracle."""
-    exe = _build_compat(tmp_path)
+    exe = _build_compat()
     W, H, nf = 752, 480, 1200
     L, R = synth.stereo_pair(W, H, 70)
     c, d = synth.frame(W, H, 80, "pan"), synth.frame(W, H, 81, "pan")
@@ -143,7 +129,7 @@ def test_reference_shaped_concurrent_call_sites(gpu, oracle, tmp_path):
         (tmp_path / (name + ".raw")).write_bytes(np.ascontiguousarray(im).tobytes())
         paths.append(str(tmp_path / (name + ".raw")))
     out = tmp_path / "out.bin"
-    subprocess.check_call([str(exe)] + paths + [str(W), str(H), str(nf), "6", str(out)], timeout=120)
+    subprocess.check_call([exe] + paths + [str(W), str(H), str(nf), "6", str(out)], timeout=120)
     raw = out.read_bytes()
     nl, nr, n1, nm, dist = np.frombuffer(raw[:20], np.int32).tolist()
     off = 20

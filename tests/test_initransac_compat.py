@@ -9,28 +9,20 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
-CPP = os.path.join(ROOT, "tests", "cpp")
+import native
 
 
-def _build(tmp_path):
-    exe, ref = tmp_path / "initransac_compat_main", tmp_path / "initransac_ref.o"
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-Wall", "-c", os.path.join(CPP, "initransac_ref.c"),
-                           "-o", str(ref)])
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-I", os.path.join(PKG, "cpp"), "-I", CPP,
-                           os.path.join(CPP, "initransac_compat_main.cpp"), str(ref), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-lm", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("initransac_compat_main.cpp", ("initransac_ref.c",), ("-pthread",))
 
 
-def test_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 @pytest.mark.gpu
 def test_compat_members_equal_the_restatement(gpu, tmp_path):
-    r = subprocess.run([str(_build(tmp_path))], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([_build()], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "initransac_compat_main: 0 failures" in r.stdout
     assert "draw: 4 of 4 set tables equal the restated draw" in r.stdout

@@ -9,32 +9,20 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
-CPP = os.path.join(ROOT, "tests", "cpp")
+import native
 
 
-def _build(tmp_path):
-    exe = tmp_path / "initrecon_compat_main"
-    objs = []
-    for name in ("initransac_ref", "initrecon_ref"):
-        o = tmp_path / (name + ".o")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-strict-aliasing", "-Wall", "-c",
-                               os.path.join(CPP, name + ".c"), "-o", str(o)])
-        objs.append(str(o))
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-I", os.path.join(PKG, "cpp"), "-I", CPP,
-                           os.path.join(CPP, "initrecon_compat_main.cpp")] + objs +
-                          ["-o", str(exe), "-L", PKG, "-lorbx", "-lm", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("initrecon_compat_main.cpp", ("initransac_ref.c", "initrecon_ref.c"), ("-pthread",))
 
 
-def test_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 @pytest.mark.gpu
 def test_initialize_equals_the_restatement(gpu, tmp_path):
-    r = subprocess.run([str(_build(tmp_path))], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([_build()], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "initrecon_compat_main: 0 failures" in r.stdout
     assert "false path: vP3D and vbTriangulated untouched" in r.stdout

@@ -8,28 +8,22 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
-CPP = os.path.join(ROOT, "tests", "cpp")
+import native
 
 
-def _build(tmp_path):
-    exe = tmp_path / "init_compat_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(PKG, "cpp"), "-I", CPP,
-                           os.path.join(CPP, "init_compat_main.cpp"), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("init_compat_main.cpp")
 
 
-def test_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 @pytest.mark.gpu
 def test_compat_member_equals_the_host_loop(gpu, tmp_path):
-    exe = _build(tmp_path)
+    exe = _build()
     out = tmp_path / "out.txt"
-    subprocess.check_call([str(exe), "7", str(out)], timeout=120)
+    subprocess.check_call([exe, "7", str(out)], timeout=120)
     got = {"H": [], "D": []}
     for line in out.read_text().split("\n"):
         w = line.split()

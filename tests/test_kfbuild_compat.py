@@ -10,24 +10,16 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
-CPP = os.path.join(ROOT, "tests", "cpp")
+import native
+from native import PKG
 
 
-def _build(tmp_path):
-    ref = tmp_path / "kfbuild_ref.o"
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-Wall", "-c", os.path.join(CPP, "kfbuild_ref.c"),
-                           "-o", str(ref)])
-    exe = tmp_path / "kfbuild_compat_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(PKG, "cpp"), "-I", CPP,
-                           os.path.join(CPP, "kfbuild_compat_main.cpp"), str(ref), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-lm", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("kfbuild_compat_main.cpp", ("kfbuild_ref.c",))
 
 
-def test_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 def test_switch_defaults_to_the_host_projection():
@@ -37,9 +29,9 @@ def test_switch_defaults_to_the_host_projection():
 
 @pytest.mark.gpu
 def test_device_projection_members_equal_restatement_and_walk(gpu, tmp_path):
-    exe = _build(tmp_path)
+    exe = _build()
     out = tmp_path / "out.txt"
-    subprocess.check_call([str(exe), "7", str(out)], timeout=120)
+    subprocess.check_call([exe, "7", str(out)], timeout=120)
     got, counts = {}, None
     for line in out.read_text().split("\n"):
         w = line.split()

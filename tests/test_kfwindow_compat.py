@@ -11,11 +11,10 @@ import subprocess
 
 import pytest
 
+import native
+from native import CPP, ROOT
 from test_signatures import COMPAT, REF, _params, _strip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
-CPP = os.path.join(ROOT, "tests", "cpp")
 
 # include/ORBmatcher.h:56-62; used where the reference header is absent and
 # checked against it where it is present
@@ -88,23 +87,19 @@ def test_probe_rejects_drifted_signatures(tmp_path):
     assert _probe(tmp_path, [("Fuse", ("std::vector<KeyFrame*>",) + _BATCHED[1:])]).returncode != 0
 
 
-def _build(tmp_path):
-    exe = tmp_path / "kfwin_compat_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(PKG, "cpp"), "-I", CPP,
-                           os.path.join(CPP, "kfwin_compat_main.cpp"), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("kfwin_compat_main.cpp")
 
 
-def test_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 @pytest.mark.gpu
 def test_compat_members_equal_the_host_loop(gpu, tmp_path):
-    exe = _build(tmp_path)
+    exe = _build()
     out = tmp_path / "out.txt"
-    subprocess.check_call([str(exe), "7", str(out)], timeout=120)
+    subprocess.check_call([exe, "7", str(out)], timeout=120)
     got = {}
     for line in out.read_text().split("\n"):
         w = line.split()

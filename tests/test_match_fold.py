@@ -16,14 +16,12 @@ equal a CPU model of the fold (the hash of csrc/match_fold_hash.h, built for
 the host from tests/cpp/match_fold_hash.c).
 """
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "match_fold_hash.c")
+import native
+
 KCAP = 130
 NNR = 0.75
 CAP = 66  # orbm_dcap(0.75): candidates at or above it cannot change a decision
@@ -33,10 +31,8 @@ CAP = 66  # orbm_dcap(0.75): candidates at or above it cannot change a decision
 # the fold on the CPU
 # --------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def foldhash(tmp_path_factory):
-    so = tmp_path_factory.mktemp("foldhash") / "libfoldhash.so"
-    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-Wall", "-o", str(so), SRC])
-    L = ctypes.CDLL(str(so))
+def foldhash():
+    L = native.ref_lib("match_fold_hash.c")
     L.fold_slots.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     L.fold_slots.restype = None
     return L

@@ -18,6 +18,8 @@ import re
 import numpy as np
 import pytest
 
+import native
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INC = os.path.join(ROOT, "orb-slam-system_amd", "csrc", "sincos_exceptions.inc")
 
@@ -111,19 +113,12 @@ def test_device_sincos_matches_table_and_core(gpu):
             "x=0x%08x: device (0x%08x, 0x%08x) vs (0x%08x, 0x%08x)" % (b, got[i, 0], got[i, 1], *want)
 
 
-def _build_exhaustive(tmp_path):
-    import subprocess
-    exe = tmp_path / "sincos_exhaustive"
-    pkg = os.path.join(ROOT, "orb-slam-system_amd")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-ffp-contract=off", "-I",
-                           os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "sincos_exhaustive.cpp"), "-o", str(exe),
-                           "-L", pkg, "-lorbx", "-Wl,-rpath," + pkg])
-    return exe
+def _build_exhaustive():
+    return native.program("sincos_exhaustive.cpp", extra=("-pthread", "-ffp-contract=off", "-I", native.INCLUDE))
 
 
-def test_exhaustive_checker_compiles(tmp_path):
-    assert _build_exhaustive(tmp_path).exists()
+def test_exhaustive_checker_compiles():
+    assert os.path.exists(_build_exhaustive())
 
 
 @pytest.mark.gpu
@@ -134,9 +129,9 @@ def test_device_sincos_exhaustive(gpu, tmp_path):
     GPU box (committed under profiles/)."""
     import json
     import subprocess
-    exe = _build_exhaustive(tmp_path)
+    exe = _build_exhaustive()
     out = tmp_path / "sincos.json"
-    r = subprocess.run([str(exe), str(out), "16"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe, str(out), "16"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     res = json.loads(out.read_text())
     assert res["inputs"] == 0x40c90fdb + 1 and res["position_changing"] == 0

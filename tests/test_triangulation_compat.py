@@ -9,11 +9,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import native
+from native import ROOT
 import triangulation_util as T
 from test_signatures import COMPAT, REF, _params, _strip
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "orb-slam-system_amd")
 
 # include/ORBmatcher.h:51-52; used where the reference header is absent and
 # checked against it where it is present
@@ -78,16 +78,12 @@ def test_search_for_triangulation_probe_rejects_drifted_signature(tmp_path):
     assert _tri_probe(tmp_path, p[:1] + ("KeyFrame&",) + p[2:]).returncode != 0
 
 
-def _build(tmp_path):
-    exe = tmp_path / "tri_compat_main"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(PKG, "cpp"),
-                           os.path.join(ROOT, "tests", "cpp", "tri_compat_main.cpp"), "-o", str(exe),
-                           "-L", PKG, "-lorbx", "-Wl,-rpath," + PKG])
-    return exe
+def _build():
+    return native.program("tri_compat_main.cpp")
 
 
-def test_call_site_compiles(tmp_path):
-    assert _build(tmp_path).exists()
+def test_call_site_compiles():
+    assert os.path.exists(_build())
 
 
 def _write_kf(f, k):
@@ -103,7 +99,7 @@ def _write_kf(f, k):
 
 @pytest.mark.gpu
 def test_compat_overloads_return_restatement_pairs(gpu, tmp_path):
-    exe = _build(tmp_path)
+    exe = _build()
     nodes1 = {3 * j + 1: 8 + (5 * j) % 11 for j in range(8)}
     kf1, kf2s, Fs = T.make_case(31, nodes1, [{3 * j + 1: 4 + (7 * j + 3 * p) % 13 for j in range(8) if (j + p) % 4}
                                              for p in range(3)])
@@ -117,7 +113,7 @@ def test_compat_overloads_return_restatement_pairs(gpu, tmp_path):
         for F in Fs:
             f.write(np.ascontiguousarray(F, np.float32).tobytes())
     out = tmp_path / "out.txt"
-    subprocess.check_call([str(exe), str(tmp_path / "in.bin"), str(out)], timeout=120)
+    subprocess.check_call([exe, str(tmp_path / "in.bin"), str(out)], timeout=120)
     # vMatchedPairs (ORBmatcher.cc:459-465): the matched rows in ascending i
     want = [[(int(i), int(m[p, i])) for i in range(m.shape[1]) if m[p, i] >= 0] for p in range(len(kf2s))]
     got = {"S": [[] for _ in kf2s], "B": [[] for _ in kf2s]}

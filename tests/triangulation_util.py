@@ -4,17 +4,12 @@ with ctypes) and the planted inputs (two synthetic poses, descriptors in
 clusters, keypoints = projections + noise).  No GPU, no orbx import."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "triangulation_ref.c")
+import native
+from native import KEYPOINT_DTYPE, ROOT, ptr as _ptr  # noqa: F401
 
-KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
-                           ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 NLEVELS = 8
 FX, FY, CX, CY = 500.0, 500.0, 320.0, 240.0
 
@@ -28,11 +23,7 @@ class Frame(ctypes.Structure):  # tri_frame == orbx_tri_frame
 
 @functools.lru_cache(maxsize=None)
 def ref_lib():
-    d = tempfile.mkdtemp(prefix="tri_ref_")
-    so = os.path.join(d, "libtriref.so")
-    subprocess.check_call(["gcc", "-O2", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-Wall",
-                           "-o", so, SRC, "-lm"])
-    lib = ctypes.CDLL(so)
+    lib = native.ref_lib("triangulation_ref.c")
     f32, vp, ci = ctypes.c_float, ctypes.c_void_p, ctypes.c_int
     for name in ("tri_check_epipolar", "tri_check_epipolar_written"):
         fn = getattr(lib, name)
@@ -41,10 +32,6 @@ def ref_lib():
     lib.tri_three_maxima.restype, lib.tri_three_maxima.argtypes = None, [vp, ci, vp]
     lib.tri_search.restype, lib.tri_search.argtypes = ci, [vp, vp, vp, ci, ci, ci, vp, vp]
     return lib
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _struct(k, keep):
