@@ -1121,9 +1121,12 @@ int orbm_initializer_reconstruct(int npair, const orbx_recon_pair* pairs, float 
 int orbm_compute_distinctive_descriptors(const uint8_t* desc, const int32_t* off, int nmp,
                                          int device, int32_t* best);
 /* Frame::UndistortKeyPoints (src/Frame.cc:384-414): K = mK (3x3 row-major,
- * CV_32F), dist = mDistCoef (ndist = 4 or 5: k1 k2 p1 p2 [k3]).  k1 == 0
+ * CV_32F), dist = mDistCoef, ndist = 0 .. 14 in OpenCV's order: k1 k2 p1 p2
+ * [k3 [k4 k5 k6 [s1 s2 s3 s4 [tauX tauY]]]], missing ones 0.  k1 == 0
  * copies the keypoints (:386-390); otherwise cv::undistortPoints(.., K, D,
- * noArray(), K) (OpenCV 3.4: double, 5 iterations).  out may equal kps. */
+ * noArray(), K) (OpenCV 3.4: double, 5 iterations).  The tilt model is not
+ * implemented: a non-zero tauX or tauY is ORBX_ERR_UNSUPPORTED (checked after
+ * the k1 == 0 copy, before any device work).  out may equal kps. */
 int orbx_undistort_keypoints(const orbx_keypoint* kps, int n, const float* K, const float* dist,
                              int ndist, int device, orbx_keypoint* out);
 

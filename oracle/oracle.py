@@ -399,6 +399,10 @@ def undistort_keypoints(kps, K, dist):
     k = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
     K9 = np.ascontiguousarray(K, np.float32).reshape(9)
     D = np.ascontiguousarray(dist, np.float32).reshape(-1)
+    if len(D) > 0 and D[0] != 0 and np.any(D[12:14] != 0):
+        # OpenCV applies the inverse tilt matrix for a non-zero tauX or tauY;
+        # oo_undistort_keypoints has no tilt model (k1 == 0 copies before that)
+        raise OracleError(OO_ERR_UNSUPPORTED)
     out = np.zeros_like(k)
     lib().oo_undistort_keypoints(_p(k), len(k), _p(K9), _p(D), len(D), _p(out))
     return out

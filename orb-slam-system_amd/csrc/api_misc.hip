@@ -59,6 +59,10 @@ extern "C" int orbx_undistort_keypoints(const orbx_keypoint* kps, int n, const f
     memmove(out, kps, n * sizeof(orbx_keypoint));
     return ORBX_OK;
   }
+  /* tauX, tauY: cvUndistortPointsInternal applies the inverse tilt matrix when
+   * either is non-zero; that is not restated here */
+  for (int j = 12; j < ndist; ++j)
+    if (dist[j] != 0.0f) return ORBX_ERR_UNSUPPORTED;
   int rc = select_device(device);
   if (rc) return rc;
   UndistortArgs A;
