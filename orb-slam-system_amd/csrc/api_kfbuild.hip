@@ -12,6 +12,7 @@
 #include "../../include/orbx.h"
 #include "call_arena.h"
 #include "kfbuild_internal.h"
+#include "plan_table.h"
 #include "projbuild_internal.h"
 
 namespace orbx {
@@ -25,25 +26,15 @@ __global__ void k_kfwin_search_plan(const KfwPlanProblem*);
 
 using namespace orbx;
 
-// PredictScale thresholds of one (log_scale_factor, nlevels), kept per plan
-struct KfThrEntry {
-  float lsf;
-  int nlevels;
-  float thr[ORBX_PROJ_MAX_LEVELS];
-};
-
 struct orbm_kf_plan {
   int device = 0, max_prob = 0, max_n = 0, max_nq = 0;
-  DevBuf<KfBuildProblem> d_bprobs;  // the projection's problem table and its pinned staging
-  PinnedBuf<KfBuildProblem> h_bprobs;
-  DevBuf<KfwPlanProblem> d_probs;  // the search's
-  PinnedBuf<KfwPlanProblem> h_probs;
-  Event ev;       // the last table upload (the staging is reusable after it)
-  Event ev_done;  // the last call's kernels (the scratch below is free after it)
+  PlanTable<KfBuildProblem> bprobs;  // the projection's problem table
+  PlanTable<KfwPlanProblem> probs;   // the search's
+  PlanFence fence;
   DevBuf<int> d_cell_off;    // max_prob x (KFW_CELLS + 1)
   DevBuf<KfwRec> d_rec;      // max_prob x max_n
   DevBuf<orbx_kf_query> d_q; // max_prob x max_nq: rows of a project_search call that names none
-  std::vector<KfThrEntry> thr_cache;
+  PredictScaleCache thr_cache;
   ~orbm_kf_plan() { hipSetDevice(device); }
 };
 
@@ -155,11 +146,9 @@ extern "C" int orbm_kf_plan_create(int max_problems, int max_n, int max_queries,
   p->max_prob = max_problems;
   p->max_n = max_n;
   p->max_nq = max_queries;
-  p->thr_cache.reserve(16);
   const size_t B = (size_t)max_problems, QS = (size_t)std::max(max_queries, 1);
-  if (p->d_bprobs.alloc(B) || p->h_bprobs.alloc(B) || p->d_probs.alloc(B) || p->h_probs.alloc(B) ||
-      p->ev.create(hipEventDisableTiming) || p->ev_done.create(hipEventDisableTiming) ||
-      p->d_cell_off.alloc(B * (KFW_CELLS + 1)) || p->d_rec.alloc(B * (size_t)max_n) || p->d_q.alloc(B * QS))
+  if (p->bprobs.alloc(B) || p->probs.alloc(B) || p->fence.create() || p->d_cell_off.alloc(B * (KFW_CELLS + 1)) ||
+      p->d_rec.alloc(B * (size_t)max_n) || p->d_q.alloc(B * QS))
     return ORBX_ERR_HIP;  // the owners release what was acquired
   *out = p.release();
   return ORBX_OK;
@@ -168,19 +157,6 @@ extern "C" int orbm_kf_plan_create(int max_problems, int max_n, int max_queries,
 extern "C" int orbm_kf_plan_destroy(orbm_kf_plan* p) {
   delete p;
   return ORBX_OK;
-}
-
-// the plan's threshold table of (lsf, nlevels), built on first use
-static const float* plan_thresholds(orbm_kf_plan* p, float lsf, int nlevels) {
-  for (const KfThrEntry& e : p->thr_cache)
-    if (e.nlevels == nlevels && memcmp(&e.lsf, &lsf, 4) == 0) return e.thr;
-  if (p->thr_cache.size() >= 16) p->thr_cache.clear();
-  KfThrEntry e = {};
-  e.lsf = lsf;
-  e.nlevels = nlevels;
-  predict_scale_thresholds_host(lsf, nlevels, e.thr);
-  p->thr_cache.push_back(e);
-  return p->thr_cache.back().thr;
 }
 
 static int plan_run(orbm_kf_plan* p, int form, int nprob, const orbx_kf_problem* probs, float th, bool project,
@@ -209,17 +185,14 @@ static int plan_run(orbm_kf_plan* p, int form, int nprob, const orbx_kf_problem*
   ORBX_TRY(hipSetDevice(p->device));
   const size_t QS = (size_t)std::max(p->max_nq, 1);
   hipStream_t s = (hipStream_t)stream;
-  ORBX_TRY(hipEventSynchronize(p->ev));            // the staging tables are free again
-  ORBX_TRY(hipStreamWaitEvent(s, p->ev_done, 0));  // and, on the device, the plan's scratch
+  if (p->fence.begin(s)) return ORBX_ERR_HIP;
   for (int i = 0; i < nprob; ++i) {
     const orbx_kf_problem& b = probs[i];
     orbx_kf_query* rows = (project && search && !b.q) ? p->d_q + (size_t)i * QS : b.q;
     if (project) {
-      KfBuildProblem& H = p->h_bprobs[i];
+      KfBuildProblem& H = p->bprobs[i];
       H.cam = b.camera;
-      memset(H.thr, 0, sizeof(H.thr));
-      const float* thr = plan_thresholds(p, b.camera.log_scale_factor, b.camera.nlevels);
-      memcpy(H.thr, thr, sizeof(float) * (size_t)(b.camera.nlevels - 1));
+      p->thr_cache.fill(b.camera.log_scale_factor, b.camera.nlevels, H.thr);
       H.pts = b.points;
       H.npts = b.npts;
       H.desc_base = 0;
@@ -229,7 +202,7 @@ static int plan_run(orbm_kf_plan* p, int form, int nprob, const orbx_kf_problem*
       H.n_nonfinite = b.n_nonfinite;
     }
     if (search) {
-      KfwPlanProblem& P = p->h_probs[i];
+      KfwPlanProblem& P = p->probs[i];
       memset(&P, 0, sizeof(P));
       if (b.npts > 0) {  // a problem without queries is not gridded (cell_off stays NULL)
         P.kf.n = b.frame.n;
@@ -249,23 +222,17 @@ static int plan_run(orbm_kf_plan* p, int form, int nprob, const orbx_kf_problem*
       }
     }
   }
-  if (project)
-    ORBX_TRY(hipMemcpyAsync(p->d_bprobs, p->h_bprobs, (size_t)nprob * sizeof(KfBuildProblem),
-                            hipMemcpyHostToDevice, s));
-  if (search)
-    ORBX_TRY(hipMemcpyAsync(p->d_probs, p->h_probs, (size_t)nprob * sizeof(KfwPlanProblem),
-                            hipMemcpyHostToDevice, s));
-  ORBX_TRY(hipEventRecord(p->ev, s));
-  if (project) launch_build(p->d_bprobs, nprob, max_npts, form, th, s);
+  if ((project && p->bprobs.upload((size_t)nprob, s)) || (search && p->probs.upload((size_t)nprob, s)) ||
+      p->fence.staged(s))
+    return ORBX_ERR_HIP;
+  if (project) launch_build(p->bprobs.dev(), nprob, max_npts, form, th, s);
   if (search && max_npts > 0) {
     const int qpb = KFW_BLOCK / KFW_G;
-    hipLaunchKernelGGL(k_kfwin_grid_kp, dim3((unsigned)nprob), dim3(1024), 0, s, p->d_probs);
+    hipLaunchKernelGGL(k_kfwin_grid_kp, dim3((unsigned)nprob), dim3(1024), 0, s, p->probs.dev());
     hipLaunchKernelGGL(k_kfwin_search_plan, dim3((unsigned)((max_npts + qpb - 1) / qpb), (unsigned)nprob),
-                       dim3(KFW_BLOCK), 0, s, p->d_probs);
+                       dim3(KFW_BLOCK), 0, s, p->probs.dev());
   }
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  ORBX_TRY(hipEventRecord(p->ev_done, s));
-  return ORBX_OK;
+  return p->fence.end(s);
 }
 
 extern "C" int orbm_kf_plan_search(orbm_kf_plan* plan, int nprob, const orbx_kf_problem* problems, void* stream) {

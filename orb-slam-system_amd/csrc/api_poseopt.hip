@@ -8,18 +8,16 @@
 #include <vector>
 
 #include "../../include/orbx.h"
-#include "api_common.h"
 #include "call_arena.h"
+#include "plan_table.h"
 #include "poseopt_internal.h"
 
 using namespace orbx;
 
 struct orbm_pose_plan {
   int device = 0, max_prob = 0, max_n = 0;
-  DevBuf<orbx_pose_problem> d_probs;
-  PinnedBuf<orbx_pose_problem> h_probs;  // pinned staging of the problem table
-  Event ev;                              // the last table upload (h_probs reusable after it)
-  Event ev_done;                         // the last call's kernel (d_probs free after it)
+  PlanTable<orbx_pose_problem> probs;
+  PlanFence fence;
   ~orbm_pose_plan() { hipSetDevice(device); }
 };
 
@@ -121,9 +119,7 @@ extern "C" int orbm_pose_plan_create(int max_problems, int max_n, int device, or
   p->max_prob = max_problems;
   p->max_n = max_n;
   const size_t B = (size_t)max_problems;
-  if (p->d_probs.alloc(B) || p->h_probs.alloc(B) || p->ev.create(hipEventDisableTiming) ||
-      p->ev_done.create(hipEventDisableTiming))
-    return ORBX_ERR_HIP;  // the owners release what was acquired
+  if (p->probs.alloc(B) || p->fence.create()) return ORBX_ERR_HIP;  // the owners release what was acquired
   *out = p.release();
   return ORBX_OK;
 }
@@ -144,14 +140,9 @@ extern "C" int orbm_pose_plan_optimize(orbm_pose_plan* p, int nprob, const orbx_
   if (nprob == 0) return ORBX_OK;
   ORBX_TRY(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
-  ORBX_TRY(hipEventSynchronize(p->ev));            // the staging table is free again
-  ORBX_TRY(hipStreamWaitEvent(s, p->ev_done, 0));  // and, on the device, the plan's table
-  memcpy(p->h_probs, probs, (size_t)nprob * sizeof(orbx_pose_problem));
-  ORBX_TRY(hipMemcpyAsync(p->d_probs, p->h_probs, (size_t)nprob * sizeof(orbx_pose_problem),
-                          hipMemcpyHostToDevice, s));
-  ORBX_TRY(hipEventRecord(p->ev, s));
-  launch_pose(p->d_probs, nprob, s);
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  ORBX_TRY(hipEventRecord(p->ev_done, s));
-  return ORBX_OK;
+  if (p->fence.begin(s)) return ORBX_ERR_HIP;
+  memcpy(p->probs.host(), probs, (size_t)nprob * sizeof(orbx_pose_problem));
+  if (p->probs.upload((size_t)nprob, s) || p->fence.staged(s)) return ORBX_ERR_HIP;
+  launch_pose(p->probs.dev(), nprob, s);
+  return p->fence.end(s);
 }

@@ -114,8 +114,7 @@ extern "C" int orbm_proj_plan_create(int max_problems, int max_n, int max_nq, in
   p->max_nq = max_nq;
   const size_t B = (size_t)max_problems;
   const size_t Q = B * (size_t)std::max(max_nq, 1);
-  if (p->d_probs.alloc(B) || p->h_probs.alloc(B) || p->ev.create(hipEventDisableTiming) ||
-      p->ev_done.create(hipEventDisableTiming) || p->d_cell_off.alloc(B * (PG_CELLS + 1)) ||
+  if (p->probs.alloc(B) || p->fence.create() || p->d_cell_off.alloc(B * (PG_CELLS + 1)) ||
       p->d_cell_feat.alloc(B * (size_t)max_n) || p->d_cand.alloc(Q * PJ_T) || p->d_ncand.alloc(Q) ||
       set_max_dynamic_lds((const void*)k_grid_build, device) ||
       set_max_dynamic_lds((const void*)k_proj_resolve, device))
@@ -136,44 +135,21 @@ extern "C" int orbm_proj_plan_search(orbm_proj_plan* p, int mode, int nprob, con
   int max_n = 1, max_nq = 0;
   for (int i = 0; i < nprob; ++i) {
     const orbx_proj_problem& q = probs[i];
-    const orbx_proj_frame& F = q.frame;
-    if (F.n < 0 || F.n > p->max_n || q.nq < 0 || q.nq > p->max_nq || !q.match || !q.nmatches ||
-        (F.n > 0 && (!F.keys || !F.desc)) || (q.nq > 0 && (!q.q || !q.qdesc)))
+    if (!frame_ok(q.frame, p->max_n) || q.nq < 0 || q.nq > p->max_nq || !q.match || !q.nmatches ||
+        (q.nq > 0 && (!q.q || !q.qdesc)))
       return ORBX_ERR_ARG;
-    max_n = std::max(max_n, F.n);
+    max_n = std::max(max_n, q.frame.n);
     max_nq = std::max(max_nq, q.nq);
   }
   if (nprob == 0) return ORBX_OK;
   ORBX_TRY(hipSetDevice(p->device));
   hipStream_t s = (hipStream_t)stream;
-  ORBX_TRY(hipEventSynchronize(p->ev));  // the previous call's table has left the staging buffer
-  // every call reuses the plan's device scratch (problem table, grids,
-  // candidates): a call on another stream than the previous one's must not
-  // overwrite them under the previous call's kernels -- the
-  // stream waits for them on the device; no host block
-  ORBX_TRY(hipStreamWaitEvent(s, p->ev_done, 0));
+  if (p->fence.begin(s)) return ORBX_ERR_HIP;
   for (int i = 0; i < nprob; ++i) {
     const orbx_proj_problem& q = probs[i];
-    ProjProblem& P = p->h_probs[i];
-    P.F = proj_frame(&q.frame);
-    P.keys = q.frame.keys;
-    P.desc = q.frame.desc;
-    P.uright = q.frame.uright;
-    P.occupied = q.frame.occupied;
-    P.qs = q.q;
-    P.qdesc = q.qdesc;
-    P.nq = q.nq;
-    P.match = q.match;
-    P.nmatches = q.nmatches;
-    P.cell_off = p->d_cell_off + (size_t)i * (PG_CELLS + 1);
-    P.cell_feat = p->d_cell_feat + (size_t)i * p->max_n;
-    P.cand = p->d_cand + (size_t)i * std::max(p->max_nq, 1) * PJ_T;
-    P.ncand = p->d_ncand + (size_t)i * std::max(p->max_nq, 1);
+    fill_search_row(p, i, q.frame, q.q, q.qdesc, q.nq, q.match, q.nmatches);
   }
-  ORBX_TRY(hipMemcpyAsync(p->d_probs, p->h_probs, (size_t)nprob * sizeof(ProjProblem), hipMemcpyHostToDevice, s));
-  ORBX_TRY(hipEventRecord(p->ev, s));
-  launch_proj(p->d_probs, nprob, max_n, max_nq, mode, nnratio, th_dist, check_ori, s);
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  ORBX_TRY(hipEventRecord(p->ev_done, s));
-  return ORBX_OK;
+  if (p->probs.upload((size_t)nprob, s) || p->fence.staged(s)) return ORBX_ERR_HIP;
+  launch_proj(p->probs.dev(), nprob, max_n, max_nq, mode, nnratio, th_dist, check_ori, s);
+  return p->fence.end(s);
 }

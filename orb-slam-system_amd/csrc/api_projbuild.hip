@@ -141,19 +141,6 @@ extern "C" int orbm_project_points(int mode, int nprob, const orbx_proj_camera* 
   return ORBX_OK;
 }
 
-// the plan's threshold table of (lsf, nlevels), built on first use
-static const float* plan_thresholds(orbm_proj_plan* p, float lsf, int nlevels) {
-  for (const ProjThrEntry& e : p->thr_cache)
-    if (e.nlevels == nlevels && memcmp(&e.lsf, &lsf, 4) == 0) return e.thr;
-  if (p->thr_cache.size() >= 16) p->thr_cache.clear();
-  ProjThrEntry e = {};
-  e.lsf = lsf;
-  e.nlevels = nlevels;
-  predict_scale_thresholds_host(lsf, nlevels, e.thr);
-  p->thr_cache.push_back(e);
-  return p->thr_cache.back().thr;
-}
-
 static int plan_build(orbm_proj_plan* p, int mode, int nprob, const orbx_proj_build_problem* probs,
                       const orbx_proj_params* prm, bool track, float nnratio, int th_dist, int check_ori,
                       void* stream) {
@@ -167,11 +154,10 @@ static int plan_build(orbm_proj_plan* p, int mode, int nprob, const orbx_proj_bu
         (b.npts > 0 && !points_ok(mode, b.points)))
       return ORBX_ERR_ARG;
     if (track) {
-      const orbx_proj_frame& F = b.frame;
-      if (b.npts > p->max_nq || F.n < 0 || F.n > p->max_n || !b.match || !b.nmatches ||
-          (F.n > 0 && (!F.keys || !F.desc)) || (b.npts > 0 && !b.qdesc))
+      if (b.npts > p->max_nq || !frame_ok(b.frame, p->max_n) || !b.match || !b.nmatches ||
+          (b.npts > 0 && !b.qdesc))
         return ORBX_ERR_ARG;
-      max_n = std::max(max_n, F.n);
+      max_n = std::max(max_n, b.frame.n);
     } else if (b.npts > 0 && (!b.q || !b.level)) {
       return ORBX_ERR_ARG;
     }
@@ -180,18 +166,20 @@ static int plan_build(orbm_proj_plan* p, int mode, int nprob, const orbx_proj_bu
   if (nprob == 0) return ORBX_OK;
   ORBX_TRY(hipSetDevice(p->device));
   const size_t B = (size_t)p->max_prob, QS = (size_t)std::max(p->max_nq, 1);
-  if (!p->d_bprobs && (p->d_bprobs.alloc(B) || p->h_bprobs.alloc(B))) return ORBX_ERR_HIP;
-  if (track && !p->d_q && p->d_q.alloc(B * QS)) return ORBX_ERR_HIP;
+  // the first call's acquisitions; a call that fails leaves the plan holding what it held
+  const bool first = !p->bprobs;
+  if (first && p->bprobs.alloc(B)) return ORBX_ERR_HIP;
+  if (track && !p->d_q && p->d_q.alloc(B * QS)) {
+    if (first) p->bprobs.reset();
+    return ORBX_ERR_HIP;
+  }
   hipStream_t s = (hipStream_t)stream;
-  ORBX_TRY(hipEventSynchronize(p->ev));            // the staging tables are free again
-  ORBX_TRY(hipStreamWaitEvent(s, p->ev_done, 0));  // and, on the device, the plan's scratch
+  if (p->fence.begin(s)) return ORBX_ERR_HIP;
   for (int i = 0; i < nprob; ++i) {
     const orbx_proj_build_problem& b = probs[i];
-    ProjBuildProblem& H = p->h_bprobs[i];
+    ProjBuildProblem& H = p->bprobs[i];
     H.cam = b.camera;
-    memset(H.thr, 0, sizeof(H.thr));
-    const float* thr = plan_thresholds(p, b.camera.log_scale_factor, b.camera.nlevels);
-    memcpy(H.thr, thr, sizeof(float) * (size_t)(b.camera.nlevels - 1));
+    p->thr_cache.fill(b.camera.log_scale_factor, b.camera.nlevels, H.thr);
     H.pts = b.points;
     H.npts = b.npts;
     H.q = (track && !b.q) ? p->d_q + (size_t)i * QS : b.q;
@@ -199,34 +187,13 @@ static int plan_build(orbm_proj_plan* p, int mode, int nprob, const orbx_proj_bu
     H.view_cos = b.view_cos;
     H.n_in_view = b.n_in_view;
     H.n_nonfinite = b.n_nonfinite;
-    if (track) {
-      ProjProblem& P = p->h_probs[i];
-      P.F = proj_frame(&b.frame);
-      P.keys = b.frame.keys;
-      P.desc = b.frame.desc;
-      P.uright = b.frame.uright;
-      P.occupied = b.frame.occupied;
-      P.qs = H.q;
-      P.qdesc = b.qdesc;
-      P.nq = b.npts;
-      P.match = b.match;
-      P.nmatches = b.nmatches;
-      P.cell_off = p->d_cell_off + (size_t)i * (PG_CELLS + 1);
-      P.cell_feat = p->d_cell_feat + (size_t)i * p->max_n;
-      P.cand = p->d_cand + (size_t)i * QS * PJ_T;
-      P.ncand = p->d_ncand + (size_t)i * QS;
-    }
+    if (track) fill_search_row(p, i, b.frame, H.q, b.qdesc, b.npts, b.match, b.nmatches);
   }
-  ORBX_TRY(hipMemcpyAsync(p->d_bprobs, p->h_bprobs, (size_t)nprob * sizeof(ProjBuildProblem),
-                          hipMemcpyHostToDevice, s));
-  if (track)
-    ORBX_TRY(hipMemcpyAsync(p->d_probs, p->h_probs, (size_t)nprob * sizeof(ProjProblem), hipMemcpyHostToDevice, s));
-  ORBX_TRY(hipEventRecord(p->ev, s));
-  launch_build(p->d_bprobs, nprob, max_npts, mode, prm, s);
-  if (track) launch_proj(p->d_probs, nprob, max_n, max_npts, mode, nnratio, th_dist, check_ori, s);
-  if (hipGetLastError() != hipSuccess) return ORBX_ERR_HIP;
-  ORBX_TRY(hipEventRecord(p->ev_done, s));
-  return ORBX_OK;
+  if (p->bprobs.upload((size_t)nprob, s) || (track && p->probs.upload((size_t)nprob, s)) || p->fence.staged(s))
+    return ORBX_ERR_HIP;
+  launch_build(p->bprobs.dev(), nprob, max_npts, mode, prm, s);
+  if (track) launch_proj(p->probs.dev(), nprob, max_n, max_npts, mode, nnratio, th_dist, check_ori, s);
+  return p->fence.end(s);
 }
 
 extern "C" int orbm_proj_plan_project(orbm_proj_plan* plan, int mode, int nprob,

@@ -79,6 +79,36 @@ inline void predict_scale_thresholds_host(float log_scale_factor, int nlevels, f
   }
 }
 
+// the threshold tables of the (log_scale_factor, nlevels) pairs a plan has
+// met, each built on first use; 16 entries, cleared when full
+struct PredictScaleCache {
+  struct Entry {
+    float lsf;
+    int nlevels;
+    float thr[ORBX_PROJ_MAX_LEVELS];
+  };
+  Entry entries[16];
+  int n = 0;
+
+  // a problem row's thr: the nlevels - 1 thresholds, zeros behind them.  lsf
+  // is matched by bit pattern
+  void fill(float lsf, int nlevels, float (&thr)[ORBX_PROJ_MAX_LEVELS]) {
+    const Entry* hit = nullptr;
+    for (int i = 0; i < n && !hit; ++i)
+      if (entries[i].nlevels == nlevels && memcmp(&entries[i].lsf, &lsf, 4) == 0) hit = &entries[i];
+    if (!hit) {
+      if (n == 16) n = 0;
+      Entry& e = entries[n++];
+      e.lsf = lsf;
+      e.nlevels = nlevels;
+      predict_scale_thresholds_host(lsf, nlevels, e.thr);
+      hit = &e;
+    }
+    memset(thr, 0, sizeof(thr));
+    memcpy(thr, hit->thr, sizeof(float) * (size_t)(nlevels - 1));
+  }
+};
+
 }  // namespace orbx
 
 #endif

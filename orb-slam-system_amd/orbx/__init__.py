@@ -389,6 +389,17 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _dptr(t):
+    """device pointer of a cuda tensor, NULL for None"""
+    return None if t is None else t.data_ptr()
+
+
+def _proj_frame(fr):
+    """ProjFrame of a dict of cuda tensors (keys, desc, uright | None, occupied | None) and the grid floats"""
+    return ProjFrame(fr["keys"].shape[0], _dptr(fr["keys"]), _dptr(fr["desc"]), _dptr(fr.get("uright")),
+                     _dptr(fr.get("occupied")), fr["min_x"], fr["min_y"], fr["grid_w_inv"], fr["grid_h_inv"])
+
+
 def device_count():
     return _lib.orbx_device_count()
 
@@ -1036,16 +1047,11 @@ class ProjPlan:
         q [nq] rows of PROJ_QUERY_DTYPE as u8 [nq, 28], qdesc [nq, 32] u8,
         match [n] i32 and nmatches [1] i32 (outputs) -- plus the grid floats
         min_x, min_y, grid_w_inv, grid_h_inv.  Asynchronous."""
-        def ptr(t):
-            return None if t is None else t.data_ptr()
         arr = (ProjProblem * max(len(problems), 1))()
         for i, pb in enumerate(problems):
-            n = pb["keys"].shape[0]
-            arr[i].frame = ProjFrame(n, ptr(pb["keys"]), ptr(pb["desc"]), ptr(pb.get("uright")),
-                                     ptr(pb.get("occupied")), pb["min_x"], pb["min_y"],
-                                     pb["grid_w_inv"], pb["grid_h_inv"])
-            arr[i].q, arr[i].qdesc, arr[i].nq = ptr(pb["q"]), ptr(pb["qdesc"]), pb["q"].shape[0]
-            arr[i].match, arr[i].nmatches = ptr(pb["match"]), ptr(pb["nmatches"])
+            arr[i].frame = _proj_frame(pb)
+            arr[i].q, arr[i].qdesc, arr[i].nq = _dptr(pb["q"]), _dptr(pb["qdesc"]), pb["q"].shape[0]
+            arr[i].match, arr[i].nmatches = _dptr(pb["match"]), _dptr(pb["nmatches"])
         _check(_lib.orbm_proj_plan_search(self._h, mode, len(problems), ctypes.cast(arr, ctypes.c_void_p),
                                           float(nnratio), int(th_dist), 1 if check_ori else 0,
                                           _stream_handle(stream)), "orbm_proj_plan_search")
@@ -1053,23 +1059,18 @@ class ProjPlan:
 
     @staticmethod
     def _build_problems(problems, track):
-        def ptr(t):
-            return None if t is None else t.data_ptr()
         arr = (ProjBuildProblem * max(len(problems), 1))()
         for i, pb in enumerate(problems):
             a = arr[i]
             a.camera = proj_camera(pb["camera"])
             pts = pb["points"]
-            a.points = ProjPoints(*[ptr(pts.get(n)) for n in POINT_FIELDS])
+            a.points = ProjPoints(*[_dptr(pts.get(n)) for n in POINT_FIELDS])
             a.npts = pts["pos"].shape[0]
             for n in ("q", "level", "view_cos", "n_in_view", "n_nonfinite"):
-                setattr(a, n, ptr(pb.get(n)))
+                setattr(a, n, _dptr(pb.get(n)))
             if track:
-                fr = pb["frame"]
-                a.frame = ProjFrame(fr["keys"].shape[0], ptr(fr["keys"]), ptr(fr["desc"]), ptr(fr.get("uright")),
-                                    ptr(fr.get("occupied")), fr["min_x"], fr["min_y"], fr["grid_w_inv"],
-                                    fr["grid_h_inv"])
-                a.qdesc, a.match, a.nmatches = ptr(pb["qdesc"]), ptr(pb["match"]), ptr(pb["nmatches"])
+                a.frame = _proj_frame(pb["frame"])
+                a.qdesc, a.match, a.nmatches = _dptr(pb["qdesc"]), _dptr(pb["match"]), _dptr(pb["nmatches"])
         return arr
 
     def project(self, mode, problems, th=1.0, viewing_cos_limit=0.5, level_rule=LEVEL_RULE_NEITHER, stream=None):
@@ -1260,8 +1261,6 @@ class KeyframePlan:
 
     @staticmethod
     def _problems(problems, project, search):
-        def ptr(t):
-            return None if t is None else t.data_ptr()
         arr = (KfProblem * max(len(problems), 1))()
         for i, pb in enumerate(problems):
             a = arr[i]
@@ -1274,13 +1273,13 @@ class KeyframePlan:
                 a.npts = pb["q"].shape[0]
             if project:
                 a.camera = kf_camera(pb["camera"])
-                a.points = KfPoints(*[ptr(pts.get(n)) for n in KF_POINT_FIELDS])
+                a.points = KfPoints(*[_dptr(pts.get(n)) for n in KF_POINT_FIELDS])
             if search:
                 fr = pb["frame"]
-                a.frame = KfFrame(fr["keys"].shape[0], ptr(fr["keys"]), ptr(fr["desc"]), fr["min_x"], fr["min_y"],
-                                  fr["grid_w_inv"], fr["grid_h_inv"])
+                a.frame = KfFrame(fr["keys"].shape[0], _dptr(fr["keys"]), _dptr(fr["desc"]), fr["min_x"],
+                                  fr["min_y"], fr["grid_w_inv"], fr["grid_h_inv"])
             for n in ("qdesc", "q", "level", "n_live", "n_nonfinite", "best_idx", "best_dist"):
-                setattr(a, n, ptr(pb.get(n)))
+                setattr(a, n, _dptr(pb.get(n)))
         return arr
 
     def search(self, problems, stream=None):
@@ -1378,8 +1377,6 @@ class PosePlan:
         match[] of ProjPlan.track as it stands) or has_point [n] u8, and the
         outputs Tcw_out [16] f32, outlier [n] u8, ninliers [1] i32 and status
         [1] i32 (features dropped for a bad octave or index)."""
-        def ptr(t):
-            return None if t is None else t.data_ptr()
         arr = (PoseProblem * max(len(problems), 1))()
         for i, pb in enumerate(problems):
             n = pb["keys"].shape[0]
@@ -1393,10 +1390,10 @@ class PosePlan:
             _check_dev(pb["status"], 4, 1, "status")
             a = arr[i]
             a.camera = pose_camera(pb["camera"])
-            a.obs = PoseObs(n, ptr(pb["keys"]), ptr(pb.get("uright")), ptr(pb["pos"]), ptr(pb.get("point_index")),
-                            ptr(pb.get("has_point")), pb["pos"].shape[0])
-            a.Tcw_out, a.outlier = ptr(pb["Tcw_out"]), ptr(pb.get("outlier"))
-            a.ninliers, a.status = ptr(pb["ninliers"]), ptr(pb["status"])
+            a.obs = PoseObs(n, _dptr(pb["keys"]), _dptr(pb.get("uright")), _dptr(pb["pos"]),
+                            _dptr(pb.get("point_index")), _dptr(pb.get("has_point")), pb["pos"].shape[0])
+            a.Tcw_out, a.outlier = _dptr(pb["Tcw_out"]), _dptr(pb.get("outlier"))
+            a.ninliers, a.status = _dptr(pb["ninliers"]), _dptr(pb["status"])
         _check(_lib.orbm_pose_plan_optimize(self._h, len(problems), ctypes.cast(arr, ctypes.c_void_p),
                                             _stream_handle(stream)), "orbm_pose_plan_optimize")
 

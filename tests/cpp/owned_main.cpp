@@ -4,8 +4,10 @@
 // exactly once; moves empty their source and free what they overwrite;
 // reset() twice is safe; alloc on a filled owner frees the old block; a vector
 // of owners frees every one; an injected failure (orbx_debug_fail_acquire)
-// leaves the owner empty; acquisitions equal releases at exit, on the owners'
-// own counter (orbx_debug_live_resources) as well.  Built by `make sanitize`.
+// leaves the owner empty; a plan's table (csrc/plan_table.h) over two such
+// owners holds both halves or neither, whichever acquisition fails;
+// acquisitions equal releases at exit, on the owners' own counter
+// (orbx_debug_live_resources) as well.  Built by `make sanitize`.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "owned.h"
+#include "plan_table.h"
 #include "expect.h"
 
 static int g_made = 0, g_freed = 0;
@@ -127,6 +130,28 @@ int main() {
     EXPECT(a.alloc(8) == ORBX_OK);
   }
   EXPECT(g_made == 47 && g_freed == 47 && live() == 0);
+
+  {  // a plan's table over two such owners: both halves or neither
+    orbx::PlanTable<char, HostBuf, HostBuf> t;
+    EXPECT(!t);
+    for (int nth = 1; nth <= 2; ++nth) {  // the device half fails, then the staging half
+      EXPECT(orbx_debug_fail_acquire(nth) == ORBX_OK);
+      EXPECT(t.alloc(8) == ORBX_ERR_HIP && !t);
+      EXPECT(t.host() == nullptr && t.dev() == nullptr);
+      EXPECT(g_made == 46 + nth && g_freed == g_made && live() == 0);
+    }
+    EXPECT(t.alloc(8) == ORBX_OK && t);  // unarmed
+    t[0] = 1;
+    t.host()[7] = 2;
+    EXPECT(t[7] == 2 && t.host()[0] == 1 && t.dev() != nullptr);
+    EXPECT(g_made == 50 && g_freed == 48 && live() == 2);
+    EXPECT(t.alloc(16) == ORBX_OK && t);  // a filled table frees the old pair
+    EXPECT(g_made == 52 && g_freed == 50 && live() == 2);
+    t[15] = 3;
+    EXPECT(orbx_debug_fail_acquire(2) == ORBX_OK);
+    EXPECT(t.alloc(8) == ORBX_ERR_HIP && !t);  // and keeps neither old half when the new staging fails
+    EXPECT(g_made == 53 && g_freed == 53 && live() == 0);
+  }
   EXPECT(orbx_debug_live_resources(nullptr) == ORBX_ERR_ARG);
 
   printf("owned: %d acquired, %d released, %d failures\n", g_made, g_freed, fails);

@@ -1,6 +1,7 @@
 // Host-side ASan/UBSan run of the device-side projection's host code
 // (csrc/projbuild_internal.h, csrc/api_projbuild.hip): the PredictScale
-// threshold builder over ordinary and extreme scales, and every argument check
+// threshold builder over ordinary and extreme scales, the plans' cache of its
+// tables (hit, miss, the clear when full), and every argument check
 // of orbm_predict_scale_thresholds / orbm_project_points / the plan methods
 // that returns before a device is needed.  No GPU is touched (the test hides
 // the devices: a well-formed call ends in ORBX_ERR_NO_DEVICE).  Built by
@@ -35,7 +36,40 @@ static void thresholds(float lsf, int nlevels) {
   }
 }
 
+// the row the plans' cache writes for (lsf, nlevels): the thresholds of
+// orbm_predict_scale_thresholds in front, zeros behind
+static void cached_row(orbx::PredictScaleCache& cache, float lsf, int nlevels) {
+  float want[ORBX_PROJ_MAX_LEVELS] = {};
+  EXPECT(orbm_predict_scale_thresholds(lsf, nlevels, want) == ORBX_OK);
+  float row[ORBX_PROJ_MAX_LEVELS];
+  memset(row, 0xff, sizeof row);
+  cache.fill(lsf, nlevels, row);
+  EXPECT(memcmp(row, want, sizeof row) == 0);
+  for (int L = nlevels > 1 ? nlevels - 1 : 0; L < ORBX_PROJ_MAX_LEVELS; ++L) EXPECT(row[L] == 0.0f);
+}
+
+static void threshold_cache() {
+  orbx::PredictScaleCache cache;
+  const float lsf = logf(1.2f);
+  const float keys[][2] = {{lsf, 8}, {lsf, 1}, {logf(2.0f), 32}, {nextafterf(lsf, 1.0f), 8}};
+  for (int pass = 0; pass < 2; ++pass) {  // the miss, then the hit
+    for (const auto& k : keys) cached_row(cache, k[0], (int)k[1]);
+    EXPECT(cache.n == 4);  // the neighbouring bit pattern of lsf is an entry of its own
+  }
+  // seventeen distinct keys in a row: the full cache is cleared, then serves again
+  orbx::PredictScaleCache full;
+  for (int i = 0; i < 17; ++i) {
+    cached_row(full, logf(1.1f + 0.01f * (float)i), 8);
+    EXPECT(full.n == (i < 16 ? i + 1 : 1));
+  }
+  cached_row(full, logf(1.1f), 8);  // the first key, gone with the clear
+  EXPECT(full.n == 2);
+  cached_row(full, logf(1.1f), 8);
+  EXPECT(full.n == 2);
+}
+
 int main() {
+  threshold_cache();
   thresholds(logf(1.2f), 8);
   thresholds(logf(2.0f), 4);
   thresholds(logf(1.05f), 12);

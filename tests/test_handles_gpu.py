@@ -30,7 +30,7 @@ N_EXTRACTOR = 0    # orbx_extractor_create plans nothing before the first image
 N_MATCH = 10       # d_probs, d_nps, d_sel, 7 scratch buffers
 N_STEREO = 5       # d_rowoff, d_rows, d_sad, d_err, stream
 N_VOCAB = 7        # 5 uploaded tables, d_err, stream
-N_PROJ = 8         # d_probs, h_probs, ev, ev_done, 4 scratch buffers
+N_PROJ = 8         # the problem table and its staging, the fence's 2 events, 4 scratch buffers
 # the extractor's plan has no d_blur (its two levels hold 392797 pixels: 1000 x 43 x 48 < 8 x that);
 # + d_img, d_kps, d_desc, d_count, h_res, h_img, h_pyr, s_copy, ev_pyr
 N_EXTRACT_NEW = N_PLAN - 1 + 9

@@ -336,11 +336,13 @@ def test_plan_resources_are_counted_and_returned(gpu):
     del plan
     assert np.array_equal(live(), before)
     # a create that fails half way leaves nothing behind, whichever acquisition fails
+    # (and the tenth attempt, with all nine made, succeeds)
     import ctypes
-    for nth in range(1, 10):
+    import test_handles_gpu as H
+
+    def create():
         h = ctypes.c_void_p()
-        gpu.lib().orbx_debug_fail_acquire(nth)
-        rc = gpu.lib().orbm_kf_plan_create(4, 500, 800, 0, ctypes.byref(h))
-        gpu.lib().orbx_debug_fail_acquire(0)
-        assert rc == gpu.ERR_HIP and not h.value, nth
-        assert np.array_equal(live(), before), nth
+        return gpu.lib().orbm_kf_plan_create(4, 500, 800, 0, ctypes.byref(h)), h
+    rc, h = H.sweep(gpu, create, 9, handle_of=lambda got: got[1])
+    assert h.value and gpu.lib().orbm_kf_plan_destroy(h) == gpu.OK
+    assert np.array_equal(live(), before)

@@ -260,7 +260,7 @@ def _plan_create(gpu, max_problems=2, max_n=300):
     return gpu.lib().orbm_pose_plan_create(max_problems, max_n, 0, ctypes.byref(h)), h
 
 
-N_POSE = 4  # d_probs, h_probs, ev, ev_done
+N_POSE = 4  # the problem table and its staging, the fence's 2 events
 
 
 def test_pose_plan_lifetime(gpu):

@@ -230,6 +230,63 @@ def test_two_calls_of_one_plan_on_two_streams(gpu):
         assert np.array_equal(pb["match"].cpu().numpy(), m) and int(pb["nmatches"].cpu()[0]) == nm
 
 
+def _rc(gpu, call):
+    try:
+        call()
+    except gpu.OrbxError as e:
+        return e.code
+    return gpu.OK
+
+
+def test_lazy_tables_survive_every_failing_acquisition(gpu):
+    """the projection's table (device rows and pinned staging) and the query
+    rows of track come with a plan's first project / track call.  Whichever of
+    these acquisitions fails, the call returns ORBX_ERR_HIP and the plan holds
+    what it held before -- a table with its staging or neither (sweep asserts
+    both) -- and the next call finds the plan usable"""
+    import torch
+    import test_handles_gpu as H
+    mode, seed = 1, 301
+    exp_m, exp_nm, _ = _track_expected(gpu, mode, seed)
+    ref = U.scene_ref(mode, NTRACK, seed, **U.MODE_ARGS[mode])
+    cam, P, qdesc, fr = _track_scene(mode, seed)
+    L, before = gpu.lib(), H.live(gpu.lib())
+
+    def project(plan, expect):
+        pb = _device_problem(torch, mode, cam, P)
+        H.sweep(gpu, lambda: _rc(gpu, lambda: plan.project(mode, [pb], **U.MODE_ARGS[mode])), expect)
+        torch.cuda.synchronize()
+        _same(_read(pb, mode), ref, mode, "project")
+        assert int(pb["n_nonfinite"].cpu()[0]) == 0
+
+    def track(plan, expect, scratch):
+        pb = _track_problem(torch, mode, cam, P, qdesc, fr, scratch=scratch)
+        call = lambda: plan.track(mode, [pb], **U.MODE_ARGS[mode], **SEARCH_ARGS[mode])
+        H.sweep(gpu, lambda: _rc(gpu, call), expect)
+        torch.cuda.synchronize()
+        assert np.array_equal(pb["match"].cpu().numpy(), exp_m) and int(pb["nmatches"].cpu()[0]) == exp_nm
+        assert int(pb["n_in_view"].cpu()[0]) == ref["n_in_view"]
+        if not scratch:
+            _same(_read(pb, mode), ref, mode, "track rows")
+
+    plan = gpu.ProjPlan(1, 400, NTRACK)  # A: the table with project, the query rows with track
+    created = H.live(L)
+    assert sum(created) - sum(before) == H.N_PROJ
+    project(plan, 2)
+    assert sum(H.live(L)) - sum(created) == 2
+    track(plan, 1, scratch=False)
+    assert sum(H.live(L)) - sum(created) == 3
+    project(plan, 0)  # nothing left to acquire
+    del plan
+    assert H.live(L) == before
+    plan = gpu.ProjPlan(1, 400, NTRACK)  # B: all three with a first track
+    track(plan, 3, scratch=True)
+    assert sum(H.live(L)) - sum(created) == 3
+    track(plan, 0, scratch=False)
+    del plan
+    assert H.live(L) == before
+
+
 # --------------------------------------------------------------------------- the deviation
 def _nonfinite_scene(mode):
     P, _ = U.planted_points([])
