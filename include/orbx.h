@@ -1111,6 +1111,72 @@ int orbm_initializer_reconstruct(int npair, const orbx_recon_pair* pairs, float 
                                  uint8_t* triangulated, const int32_t* key_off /* npair + 1 */);
 
 /* ---------------------------------------------------------------------------
+ * Sim3Solver (src/Sim3Solver.cc), batched: the constructor's
+ * per-correspondence values (camera coordinates, image points, the two error
+ * bounds) and iterate's RANSAC loop -- Horn's closed form on three point pairs
+ * per hypothesis, both reprojections of every correspondence, and the
+ * reference's sequential choice of the best and of the returning iteration --
+ * for any number of solvers in one launch.  One problem is one solver: one
+ * (current keyframe, candidate) pair after the constructor's filtering
+ * (:44-59), which stays with the caller, as does the rand() draw (:143-157).
+ * cv::eigen of the 4x4, atan2, cv::Rodrigues with its sin and cos, the centroid,
+ * the 3x3 products, Mat::dot / cv::norm and the scaled products are this
+ * library's own fixed forms ("unpinned"), not OpenCV's or libm's;
+ * Project, FromCameraToImage, the truncated bound and the comparison are
+ * pinned from the reference's object.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int ncorr;                  /* N: correspondences kept by the constructor, <= 8192        */
+  const float* pos1;          /* [ncorr][3] GetWorldPos() of pMP1                            */
+  const float* pos2;          /* [ncorr][3] GetWorldPos() of pMP2                            */
+  const float* sigma2_1;      /* [ncorr] pKF1->mvLevelSigma2[kp1.octave]                     */
+  const float* sigma2_2;      /* [ncorr] pKF2->mvLevelSigma2[kp2.octave]                     */
+  float Rcw1[9], tcw1[3];     /* pKF1->GetRotation() (row-major), GetTranslation()           */
+  float Rcw2[9], tcw2[3];     /* pKF2                                                        */
+  float fx1, fy1, cx1, cy1;   /* pKF1->mK                                                    */
+  float fx2, fy2, cx2, cy2;   /* pKF2->mK                                                    */
+  int nit;                    /* hypotheses this call evaluates, <= 4096                     */
+  const int32_t* triples;     /* [nit][3] indices into the correspondences; an index may
+                                 repeat within a triple                                      */
+  int min_inliers;            /* mRansacMinInliers                                           */
+  int fix_scale;              /* mbFixScale                                                  */
+  int best_in;                /* mnBestInliers on entry: 0 for a fresh solver, n_best of the
+                                 previous call to continue it                                */
+} orbx_sim3_problem;
+
+typedef struct {
+  int32_t it_hit;             /* the iteration at which iterate returns a transformation
+                                 (:172), -1 for none                                         */
+  int32_t it_best;            /* the iteration whose state mBest* holds on return; -1 when no
+                                 iteration reached best_in                                   */
+  int32_t n_best;             /* mnBestInliers on return (best_in when it_best is -1)        */
+  int32_t ncorr;
+  float R12[9], t12[3], s12;  /* GetEstimatedRotation / Translation / Scale; zeros when
+                                 it_best is -1                                               */
+  float sR21[9], t21[3];      /* rows 0..2 of mT21i of that iteration: orbx_kf_camera's sR21
+                                 and t21 as they stand                                       */
+} orbx_sim3_result;
+
+/* Host pointers; synchronous; safe from several threads.  With c_i the inlier
+ * count of iteration i and m_i = max(best_in, c_j for j < i): it_hit is the
+ * first i with c_i >= m_i and c_i > min_inliers; it_best is the last i <= it_hit
+ * (<= nit - 1 without a hit) with c_i >= m_i -- what the reference's sequential
+ * loop leaves (>=, so later ties replace; a count of 0 passes while best_in is
+ * 0, and a degenerate hypothesis is then reported as it is, NaNs included).
+ * inliers receives mvbBestInliers, ncorr bytes at inl_off[p] (inl_off has nprob
+ * + 1 entries; bytes past ncorr are not written); all 0 when it_best is -1.
+ * ncorr < min_inliers is valid and inert (:126): it_hit = it_best = -1 and none
+ * of the problem's arrays is read.  nprob == 0 and nit == 0 are valid.
+ * ORBX_ERR_ARG, with no output written, for a negative count (nprob, ncorr,
+ * nit, min_inliers, best_in), a required pointer that is NULL, ncorr < 3 in a
+ * problem that is not inert, a triple index outside [0, ncorr), a non-finite
+ * position, pose or camera entry, a sigma2 that is not finite, is negative or
+ * has 9.210 * sigma2 >= 2^31, inl_off[p] < 0 or inl_off[p + 1] - inl_off[p] <
+ * ncorr; ORBX_ERR_UNSUPPORTED for ncorr > 8192, nit > 4096 or nprob > 65535. */
+int orbm_sim3_solve(int nprob, const orbx_sim3_problem* problems, int device, orbx_sim3_result* res,
+                    uint8_t* inliers, const int32_t* inl_off /* nprob + 1 */);
+
+/* ---------------------------------------------------------------------------
  * SURVEY.md §8f rank 4.
  * ------------------------------------------------------------------------- */
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:222-271), batched

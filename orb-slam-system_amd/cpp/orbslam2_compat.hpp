@@ -33,9 +33,11 @@
 #define ORBX_ORBSLAM2_COMPAT_HPP
 
 #include <stdint.h>
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <list>
 #include <map>
 #include <memory>
@@ -2113,6 +2115,221 @@ class Initializer {
   bool mbComputed = false;
   orbx_ransac_result mResult;
   std::vector<uint8_t> mvInliersH, mvInliersF;
+};
+
+// ---------------------------------------------------------------------------
+// Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) over orbm_sim3_solve
+// (DESIGN.md §22): the reference's constructor with its filtering (:42-83),
+// SetRansacParameters, iterate, find and the three getters with the reference's
+// signatures, and a static IterateAll that advances several solvers by one
+// device call -- the form for the candidate loop of LoopClosing.cc:167-197.
+// KF / MP: the reference's KeyFrame and MapPoint -- reads GetMapPointMatches,
+// GetRotation, GetTranslation, mvKeysUn, mvLevelSigma2, mK; isBad,
+// GetIndexInKeyFrame, GetWorldPos.
+// One deviation: a call draws all its triples from rand() before the device
+// evaluates them, so a call that returns a transformation before its last
+// iteration has drawn triples the reference would not have; solvers that draw
+// later see a different rand() stream.  Each solver's result is the reference's
+// for the triples it was given (mvTriples keeps those of the last call).
+template <class KF, class MP>
+class Sim3Solver {
+ public:
+  Sim3Solver(KF* pKF1, KF* pKF2, const std::vector<MP*>& vpMatched12, const bool bFixScale = true)
+      : mnIterations(0), mnBestInliers(0), mbFixScale(bFixScale) {
+    mpKF1 = pKF1;
+    mpKF2 = pKF2;
+    std::vector<MP*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+    mN1 = (int)vpMatched12.size();
+    mvpMapPoints1.reserve(mN1);
+    mvpMapPoints2.reserve(mN1);
+    mvpMatches12 = vpMatched12;
+    mvnIndices1.reserve(mN1);
+    ToArray(pKF1->GetRotation(), 3, 3, mP.Rcw1);
+    ToArray(pKF1->GetTranslation(), 3, 1, mP.tcw1);
+    ToArray(pKF2->GetRotation(), 3, 3, mP.Rcw2);
+    ToArray(pKF2->GetTranslation(), 3, 1, mP.tcw2);
+    for (int i1 = 0; i1 < mN1; i1++) {
+      if (vpMatched12[i1]) {
+        MP* pMP1 = vpKeyFrameMP1[i1];
+        MP* pMP2 = vpMatched12[i1];
+        if (!pMP1) continue;
+        if (pMP1->isBad() || pMP2->isBad()) continue;
+        int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1);
+        int indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+        if (indexKF1 < 0 || indexKF2 < 0) continue;
+        const cv::KeyPoint& kp1 = pKF1->mvKeysUn[indexKF1];
+        const cv::KeyPoint& kp2 = pKF2->mvKeysUn[indexKF2];
+        mvSigma2_1.push_back(pKF1->mvLevelSigma2[kp1.octave]);  // the bounds of :67-68 are the device's
+        mvSigma2_2.push_back(pKF2->mvLevelSigma2[kp2.octave]);
+        mvpMapPoints1.push_back(pMP1);
+        mvpMapPoints2.push_back(pMP2);
+        mvnIndices1.push_back(i1);
+        float p[3];
+        ToArray(pMP1->GetWorldPos(), 3, 1, p);  // mvX3Dc1 / 2 and mvP1im1 / 2 (:75-78, :88-89) are the device's
+        mvPos1.insert(mvPos1.end(), p, p + 3);
+        ToArray(pMP2->GetWorldPos(), 3, 1, p);
+        mvPos2.insert(mvPos2.end(), p, p + 3);
+      }
+    }
+    const cv::Mat K1 = pKF1->mK, K2 = pKF2->mK;
+    mP.fx1 = K1.template at<float>(0, 0), mP.fy1 = K1.template at<float>(1, 1);
+    mP.cx1 = K1.template at<float>(0, 2), mP.cy1 = K1.template at<float>(1, 2);
+    mP.fx2 = K2.template at<float>(0, 0), mP.fy2 = K2.template at<float>(1, 1);
+    mP.cx2 = K2.template at<float>(0, 2), mP.cy2 = K2.template at<float>(1, 2);
+    SetRansacParameters();
+  }
+
+  // :94-118
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    mRansacProb = probability;
+    mRansacMinInliers = minInliers;
+    mRansacMaxIts = maxIterations;
+    N = (int)mvpMapPoints1.size();
+    float epsilon = (float)mRansacMinInliers / N;
+    int nIterations;
+    if (mRansacMinInliers == N)
+      nIterations = 1;
+    else
+      nIterations = (int)ceil(log(1 - mRansacProb) / log(1 - pow(epsilon, 3)));
+    mRansacMaxIts = std::max(1, std::min(nIterations, mRansacMaxIts));
+    mnIterations = 0;
+  }
+
+  // :120-187
+  cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, int device = 0) {
+    IterateAll(std::vector<Sim3Solver*>(1, this), nIterations, device);
+    return Collect(bNoMore, vbInliers, nInliers);
+  }
+
+  // :189-193
+  cv::Mat find(std::vector<bool>& vbInliers12, int& nInliers, int device = 0) {
+    bool bFlag;
+    return iterate(mRansacMaxIts, bFlag, vbInliers12, nInliers, device);
+  }
+
+  // nIterations iterations of every listed solver in one device call; the
+  // triples are drawn from rand() in list order.  Each solver's Collect then
+  // reports what its iterate would have returned
+  static void IterateAll(const std::vector<Sim3Solver*>& vpSolvers, int nIterations, int device = 0) {
+    const size_t n = vpSolvers.size();
+    if (n == 0) return;
+    std::vector<orbx_sim3_problem> probs(n);
+    std::vector<int32_t> off(n + 1, 0);
+    for (size_t p = 0; p < n; ++p) {
+      Sim3Solver& S = *vpSolvers[p];
+      S.mbHit = false;
+      S.mvTriples.clear();
+      int k = 0;
+      if (S.N >= S.mRansacMinInliers) {  // :126
+        if (S.N < 3) orbx_throw(ORBX_ERR_ARG, "Sim3Solver: fewer than 3 correspondences");
+        k = std::max(0, std::min(nIterations, S.mRansacMaxIts - S.mnIterations));  // :138
+      }
+      std::vector<size_t> vAvailableIndices;
+      for (int it = 0; it < k; ++it) {  // :143-157
+        vAvailableIndices.resize((size_t)S.N);
+        for (int i = 0; i < S.N; ++i) vAvailableIndices[i] = (size_t)i;
+        for (short i = 0; i < 3; ++i) {
+          int randi = Initializer::RandomInt(0, (int)vAvailableIndices.size() - 1);
+          S.mvTriples.push_back((int32_t)vAvailableIndices[randi]);
+          vAvailableIndices[randi] = vAvailableIndices.back();
+          vAvailableIndices.pop_back();
+        }
+      }
+      orbx_sim3_problem& P = probs[p];
+      P = S.mP;
+      P.ncorr = S.N;
+      P.pos1 = S.mvPos1.data(), P.pos2 = S.mvPos2.data();
+      P.sigma2_1 = S.mvSigma2_1.data(), P.sigma2_2 = S.mvSigma2_2.data();
+      P.nit = k;
+      P.triples = S.mvTriples.data();
+      P.min_inliers = S.mRansacMinInliers;
+      P.fix_scale = S.mbFixScale ? 1 : 0;
+      P.best_in = S.mnBestInliers;
+      off[p + 1] = off[p] + S.N;
+    }
+    std::vector<orbx_sim3_result> res(n);
+    std::vector<uint8_t> inl((size_t)off[n] + 1);
+    orbx_throw(orbm_sim3_solve((int)n, probs.data(), device, res.data(), inl.data(), off.data()), "Sim3Solver::iterate");
+    for (size_t p = 0; p < n; ++p) {
+      Sim3Solver& S = *vpSolvers[p];
+      const orbx_sim3_result& r = res[p];
+      S.mnIterations += r.it_hit >= 0 ? r.it_hit + 1 : probs[p].nit;  // :141
+      if (r.it_best >= 0) {  // :165-170
+        S.mResult = r;
+        S.mnBestInliers = r.n_best;
+        S.mvbBestInliers.assign(inl.begin() + off[p], inl.begin() + off[p + 1]);
+        S.mBestRotation = cv::Mat(3, 3, CV_32F);
+        S.mBestTranslation = cv::Mat(3, 1, CV_32F);
+        S.mBestT12 = cv::Mat(4, 4, CV_32F);
+        S.mBestScale = r.s12;
+        for (int i = 0; i < 4; ++i)
+          for (int j = 0; j < 4; ++j) S.mBestT12.template at<float>(i, j) = i == j ? 1.0f : 0.0f;
+        for (int i = 0; i < 3; ++i) {
+          for (int j = 0; j < 3; ++j) {
+            S.mBestRotation.template at<float>(i, j) = r.R12[3 * i + j];
+            S.mBestT12.template at<float>(i, j) = r.s12 * r.R12[3 * i + j];  // :303
+          }
+          S.mBestTranslation.template at<float>(i, 0) = r.t12[i];
+          S.mBestT12.template at<float>(i, 3) = r.t12[i];
+        }
+      }
+      S.mbHit = r.it_hit >= 0;
+    }
+  }
+
+  // the outputs of iterate after an IterateAll (:122-130, :172-186)
+  cv::Mat Collect(bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+    bNoMore = false;
+    vbInliers = std::vector<bool>(mN1, false);
+    nInliers = 0;
+    if (N < mRansacMinInliers) {
+      bNoMore = true;
+      return cv::Mat();
+    }
+    if (mbHit) {
+      nInliers = mnBestInliers;
+      for (int i = 0; i < N; i++)
+        if (mvbBestInliers[i]) vbInliers[mvnIndices1[i]] = true;
+      return mBestT12;
+    }
+    if (mnIterations >= mRansacMaxIts) bNoMore = true;
+    return cv::Mat();
+  }
+
+  cv::Mat GetEstimatedRotation() { return mBestRotation.clone(); }
+  cv::Mat GetEstimatedTranslation() { return mBestTranslation.clone(); }
+  float GetEstimatedScale() { return mBestScale; }
+
+  // the record of the iteration the best state comes from: sR21 and t21 are
+  // orbx_kf_camera's, for ORBmatcher::SearchBySim3's device form
+  const orbx_sim3_result& Result() const { return mResult; }
+
+  // the reference's members (include/Sim3Solver.h:48-97) that survive; the
+  // per-correspondence vectors it derives (:75-89) live on the device
+  KF* mpKF1;
+  KF* mpKF2;
+  std::vector<MP*> mvpMapPoints1, mvpMapPoints2, mvpMatches12;
+  std::vector<size_t> mvnIndices1;
+  int N, mN1;
+  std::vector<uint8_t> mvbBestInliers;
+  int mnIterations, mnBestInliers;
+  cv::Mat mBestT12, mBestRotation, mBestTranslation;
+  float mBestScale = 0.0f;
+  bool mbFixScale;
+  double mRansacProb;
+  int mRansacMinInliers, mRansacMaxIts;
+  std::vector<int32_t> mvTriples;  // the draw of the last call, three indices per iteration
+
+ private:
+  static void ToArray(const cv::Mat& M, int rows, int cols, float* out) {
+    if (M.rows != rows || M.cols != cols || M.type() != CV_32F) orbx_throw(ORBX_ERR_ARG, "Sim3Solver: a CV_32F matrix");
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) out[r * cols + c] = M.template at<float>(r, c);
+  }
+  orbx_sim3_problem mP = orbx_sim3_problem();  // the poses and cameras; the rest is filled per call
+  orbx_sim3_result mResult = orbx_sim3_result();
+  std::vector<float> mvPos1, mvPos2, mvSigma2_1, mvSigma2_2;
+  bool mbHit = false;
 };
 
 }  // namespace ORB_SLAM2

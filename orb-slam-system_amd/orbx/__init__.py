@@ -76,7 +76,7 @@ EXPORTED = [
     "orbm_keyframe_project", "orbm_kf_plan_create", "orbm_kf_plan_destroy", "orbm_kf_plan_search",
     "orbm_kf_plan_project", "orbm_kf_plan_project_search",
     "orbm_pose_optimization", "orbm_pose_plan_create", "orbm_pose_plan_destroy", "orbm_pose_plan_optimize",
-    "orbm_initializer_ransac", "orbm_initializer_reconstruct",
+    "orbm_initializer_ransac", "orbm_initializer_reconstruct", "orbm_sim3_solve",
 ]
 
 
@@ -252,6 +252,23 @@ RECON_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("model_used", "<i4"), ("R21", "<f
 RECON_H, RECON_F, RECON_AUTO = 0, 1, 2  # ORBX_RECON_*
 
 
+class Sim3Problem(ctypes.Structure):  # orbx_sim3_problem
+    _fields_ = [("ncorr", ctypes.c_int), ("pos1", ctypes.c_void_p), ("pos2", ctypes.c_void_p),
+                ("sigma2_1", ctypes.c_void_p), ("sigma2_2", ctypes.c_void_p),
+                ("Rcw1", ctypes.c_float * 9), ("tcw1", ctypes.c_float * 3),
+                ("Rcw2", ctypes.c_float * 9), ("tcw2", ctypes.c_float * 3),
+                ("K1", ctypes.c_float * 4), ("K2", ctypes.c_float * 4),  # fx fy cx cy of each keyframe
+                ("nit", ctypes.c_int), ("triples", ctypes.c_void_p), ("min_inliers", ctypes.c_int),
+                ("fix_scale", ctypes.c_int), ("best_in", ctypes.c_int)]
+
+
+# orbx_sim3_result
+SIM3_RESULT_DTYPE = np.dtype([("it_hit", "<i4"), ("it_best", "<i4"), ("n_best", "<i4"), ("ncorr", "<i4"),
+                              ("R12", "<f4", (3, 3)), ("t12", "<f4", (3,)), ("s12", "<f4"),
+                              ("sR21", "<f4", (3, 3)), ("t21", "<f4", (3,))])
+assert SIM3_RESULT_DTYPE.itemsize == 116
+
+
 # k_init_cand's list length per row and the feature limit (csrc/init_internal.h)
 INIT_T, INIT_MAXN = 8, 8192
 
@@ -357,6 +374,7 @@ _sig = {
     "orbm_pose_plan_optimize": (I, [P, I, P, P]),
     "orbm_initializer_ransac": (I, [I, P, I, F, I, P, P, P, P]),
     "orbm_initializer_reconstruct": (I, [I, P, F, F, I, I, P, P, P, P]),
+    "orbm_sim3_solve": (I, [I, P, I, P, P, P]),
     "orbm_compute_distinctive_descriptors": (I, [P, P, I, I, P]),
     "orbx_undistort_keypoints": (I, [P, I, P, P, I, I, P]),
     "orbx_selftest_sincos": (I, [P, I, P, P]),
@@ -922,6 +940,54 @@ def initializer_ransac(pairs, nit, sigma=1.0, device=0):
         out.append(dict(H21=r["H21"].copy(), F21=r["F21"].copy(), SH=r["SH"], SF=r["SF"], RH=r["RH"],
                         it_H=int(r["it_H"]), it_F=int(r["it_F"]), nmatch=int(r["nmatch"]),
                         inliers_H=inl_h[off[p]:off[p + 1]].copy(), inliers_F=inl_f[off[p]:off[p + 1]].copy()))
+    return out
+
+
+def sim3_problem(pr, keep):
+    """Sim3Problem of a dict as sim3_solve takes it; the arrays it points to are
+    appended to `keep`"""
+    pos1 = np.ascontiguousarray(pr["pos1"], np.float32).reshape(-1, 3)
+    pos2 = np.ascontiguousarray(pr["pos2"], np.float32).reshape(-1, 3)
+    s1 = np.ascontiguousarray(pr["sigma2_1"], np.float32).reshape(-1)
+    s2 = np.ascontiguousarray(pr["sigma2_2"], np.float32).reshape(-1)
+    tri = np.ascontiguousarray(pr["triples"], np.int32).reshape(-1, 3)
+    n = len(pos1)
+    nit = int(pr.get("nit", len(tri)))
+    if not (len(pos2) == len(s1) == len(s2) == n) or len(tri) < nit:
+        raise OrbxError(ERR_ARG, "sim3_solve: pos2, sigma2_1 and sigma2_2 need a row per correspondence, triples one per iteration")
+    keep.append((pos1, pos2, s1, s2, tri))
+    vec = lambda k, m: (ctypes.c_float * m)(*np.asarray(pr[k], np.float32).reshape(m))
+    return Sim3Problem(n, _p(pos1), _p(pos2), _p(s1), _p(s2), vec("Rcw1", 9), vec("tcw1", 3), vec("Rcw2", 9),
+                       vec("tcw2", 3), vec("K1", 4), vec("K2", 4), nit, _p(tri), int(pr["min_inliers"]),
+                       1 if pr["fix_scale"] else 0, int(pr.get("best_in", 0)))
+
+
+def sim3_solve(problems, device=0):
+    """Sim3Solver's constructor values and iterate (orbm_sim3_solve), batched
+    over solvers: dict(pos1, pos2 float32[ncorr, 3] world positions of the
+    matched map points, sigma2_1, sigma2_2 float32[ncorr], Rcw1, tcw1, Rcw2, tcw2,
+    K1, K2 = (fx, fy, cx, cy), triples int32[nit, 3] indices into the
+    correspondences, min_inliers, fix_scale, best_in = 0, nit = len(triples)).
+    Returns per problem dict(it_hit, it_best (-1: none), n_best, ncorr, R12
+    float32[3, 3], t12 float32[3], s12, sR21 float32[3, 3], t21 float32[3] as
+    orbx_kf_camera takes them, inliers uint8[ncorr])."""
+    nprob = len(problems)
+    arr = (Sim3Problem * max(nprob, 1))()
+    keep, off = [], [0]
+    for p, pr in enumerate(problems):
+        arr[p] = sim3_problem(pr, keep)
+        off.append(off[-1] + arr[p].ncorr)
+    res = np.zeros(max(nprob, 1), SIM3_RESULT_DTYPE)
+    inl_off = np.array(off, np.int32)
+    inl = np.zeros(max(off[-1], 1), np.uint8)
+    _check(_lib.orbm_sim3_solve(nprob, ctypes.cast(arr, ctypes.c_void_p), device, _p(res), _p(inl), _p(inl_off)),
+           "orbm_sim3_solve")
+    out = []
+    for p in range(nprob):
+        r = res[p]
+        d = {k: (r[k].copy() if r[k].shape else (int(r[k]) if k != "s12" else r[k])) for k in SIM3_RESULT_DTYPE.names}
+        d["inliers"] = inl[off[p]:off[p + 1]].copy()
+        out.append(d)
     return out
 
 
